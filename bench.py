@@ -11,7 +11,10 @@ once per step (weak scaling: value = views/s over all ranks).
 before anything in this process touches the GPU); under `python -m torch.distributed.run` the ranks come from the
 environment.  A mismatch between --gpus and the world size is an error, never a silent single-GPU run.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, --warmup steps, the --steps
+timed steps, the line (metric, value, unit, higher_is_better, dtype, ms_per_step, config).  --full adds every other
+measurement (per-stage times, rooflines, render rates, training steps, side workloads, CPU baseline, payload sweep).
+--dump-outputs DIR writes what the last timed step computed (write_outputs).
 """
 import argparse
 import gc
@@ -38,10 +41,20 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--workload", default="config3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other measurement of the line: per-stage times, the other "
+                         "forward mode, rooflines, render rates, training steps, side workloads, the CPU baseline and "
+                         "(multi-GPU) the payload sweep; a plain run sets up, warms up, times the steps and reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; per-gaussian arrays as a fixed, seeded sample of rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
     ap.add_argument("--no-extra-workloads", action="store_true",
-                    help="skip the non-headline workloads (half-culled config 3, dense4m) reported as extra keys")
-    return ap.parse_args()
+                    help="(with --full) skip the non-headline workloads (half-culled config 3, dense4m) reported as extra keys")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -524,6 +537,54 @@ def cpu_baseline(scene, args, params, cam, gi, cfg, N, W, H, L, do_bwd):
                                          "normal point clouds, tree build included")}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_ROWS = 65536            # per-gaussian arrays: this many rows, a fixed sample of global gaussian indices
+DUMP_SEED = 0x3D65
+DUMP_CAP_BYTES = 64 << 20
+
+
+def collect_outputs(torch, step, fwd, do_bwd, N, world):
+    """What the timed step handed its caller in the LAST timed step, copied to the host before anything else runs on
+    the context (its buffers are reused): the forward's image, final transmittance and splats per pixel, and the
+    per-gaussian gradients.  The gradients come in compacted order; they are scattered back to global gaussian order
+    (zero for culled gaussians), so that two builds compare row for row whatever order their compaction produced, and
+    sampled at DUMP_ROWS seeded global indices (saved as grad_rows).  Multi-GPU: rank 0's forward and the summed rows in
+    the packed layout (ViewShardedStep.packed)."""
+    import numpy as np
+    out = {}
+    if fwd is not None:  # (None: nothing in view on this rank)
+        out["image"] = fwd["image"].float().cpu().numpy()
+        out["transmittance"] = fwd["T"].float().cpu().numpy()
+        out["splats_per_pixel"] = fwd["n"].float().cpu().numpy()  # integer counts, exact in float32
+    if do_bwd:
+        rows = np.arange(N) if N <= DUMP_ROWS else np.sort(
+            np.random.default_rng(DUMP_SEED).choice(N, DUMP_ROWS, replace=False))
+        rows_t = torch.as_tensor(rows, dtype=torch.long, device=step.dev)
+        if world > 1:
+            out["grad_packed_rows"] = step.packed.index_select(0, rows_t).cpu().numpy()
+        elif fwd is not None:
+            M = fwd["num_culled"]
+            c2g = fwd["compact_to_global"].long()
+            for k, g in step.grads.items():
+                if g is None:
+                    continue
+                g = g[:M]
+                dense = torch.zeros((N,) + tuple(g.shape[1:]), dtype=torch.float32, device=g.device)
+                dense.index_copy_(0, c2g, g)
+                out["grad_" + k] = dense.index_select(0, rows_t).cpu().numpy()
+        out["grad_rows"] = rows.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_CAP_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_CAP_BYTES}-byte cap"
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ------------------------------------------------------------------------------------------------ one rank
 def main():
     args = parse_args()
@@ -618,20 +679,23 @@ def run_rank(args, comm, device_index):
 
     # ---- reporting passes that need no collective run BEFORE the timed region (they also leave the GPU at its
     # steady clocks, as inside a training run): workload statistics and per-stage times with every stage bracketed
-    fwd = one_step()
+    # (--full only: a plain run goes straight to its warm-up)
     P = W * H
-    S_eff = tile_max_sum(torch, fwd["n"], W, H)
-    M, S, num_pairs = fwd["num_culled"], fwd["num_splats"], fwd["num_pairs"]
-    stages = stage_pass(step.ctx, dp, dc, dgi, cfg, L, step.grads, max(5, min(args.steps, 50)), do_bwd)
-    # the same forward in the OTHER mode (lean <-> every ForwardPassData array materialised)
-    step.ctx.set_lean_forward(not lean_headline)
-    stages_other = stage_pass(step.ctx, dp, dc, dgi, cfg, L, step.grads, 10, do_bwd)
-    step.ctx.set_lean_forward(lean_headline)
-    stages_full, stages_lean = (stages_other, stages) if lean_headline else (stages, stages_other)
+    S_eff = None
+    if args.full:
+        fwd = one_step()
+        S_eff = tile_max_sum(torch, fwd["n"], W, H)
+        M, S, num_pairs = fwd["num_culled"], fwd["num_splats"], fwd["num_pairs"]
+        stages = stage_pass(step.ctx, dp, dc, dgi, cfg, L, step.grads, max(5, min(args.steps, 50)), do_bwd)
+        # the same forward in the OTHER mode (lean <-> every ForwardPassData array materialised)
+        step.ctx.set_lean_forward(not lean_headline)
+        stages_other = stage_pass(step.ctx, dp, dc, dgi, cfg, L, step.grads, 10, do_bwd)
+        step.ctx.set_lean_forward(lean_headline)
+        stages_full, stages_lean = (stages_other, stages) if lean_headline else (stages, stages_other)
 
     # the whole step in the other mode (the timed region below runs the headline's)
     ms_other_mode = None
-    if do_bwd and world == 1:
+    if args.full and do_bwd and world == 1:
         step.ctx.set_lean_forward(not lean_headline)
         for _ in range(5):
             one_step()
@@ -649,7 +713,7 @@ def run_rank(args, comm, device_index):
     # intermediate ones the reference's operator chain passes along; an optimizer needs the six leaf arrays, which is
     # what the timed step asks for -- gsplat_backward_pass takes NULL for the others)
     ms_all_gradients = None
-    if do_bwd and world == 1:
+    if args.full and do_bwd and world == 1:
         g12 = step.ctx.alloc_gradients(N, L, intermediates=True)
         for _ in range(3):
             step.ctx.rasterize_image(dp, dc, cfg, cfg["bg"], L)
@@ -668,10 +732,11 @@ def run_rank(args, comm, device_index):
     for _ in range(args.warmup):
         one_step()
     torch.cuda.synchronize()
-    # Inside the timed region only the dominant kernel is bracketed by HIP events (the roofline's launch duration):
-    # every timed stage costs two event records per step, all eight together 5 % of the step.
+    # Inside the timed region (--full) only the dominant kernel is bracketed by HIP events (the roofline's launch
+    # duration): every timed stage costs two event records per step, all eight together 5 % of the step.
     dom = "render_backward" if do_bwd else "render_forward"
-    step.ctx.set_timing(True, stages=[dom])
+    if args.full:
+        step.ctx.set_timing(True, stages=[dom])
     if world > 1:
         comm.barrier()
     torch.cuda.synchronize()
@@ -679,9 +744,10 @@ def run_rank(args, comm, device_index):
     # forward's one read-back), which arrives behind the previous step's backward -- so the host's clock after each step
     # advances by one step of GPU time, and the intervals give a median next to the wall-clock mean below.
     marks = [0.0] * args.steps
+    last = None
     t0 = time.perf_counter()
     for k in range(args.steps):
-        one_step()
+        last = one_step()
         marks[k] = time.perf_counter()
     torch.cuda.synchronize()
     if world > 1:
@@ -691,12 +757,19 @@ def run_rank(args, comm, device_index):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         comm.all_reduce_max(t)
         elapsed = float(t.item())
-    dom_ms = step.ctx.get_timing()[dom][0]
-    step.ctx.set_timing(False)
+    dom_ms = None
+    if args.full:
+        dom_ms = step.ctx.get_timing()[dom][0]
+        step.ctx.set_timing(False)
+    if not args.full:  # the workload's figures from the last timed step (a --full run took them from its first pass)
+        M, S, num_pairs = ((last["num_culled"], last["num_splats"], last["num_pairs"]) if last is not None
+                           else (0, 0, 0))
+    if args.dump_outputs and rank == 0:  # before anything else reuses the context's buffers
+        write_outputs(args.dump_outputs, collect_outputs(torch, step, last, do_bwd, N, world))
 
     # ---- the headline is measured.  Multi-GPU: its communicator is closed here; the optional comparison of the other
     # payloads runs further down on a communicator of its own (rank 0 first prepares the line the guard keeps safe).
-    sweep_on = world > 1 and do_bwd and os.environ.get("GSPLAT_BENCH_SWEEP", "1") != "0"
+    sweep_on = args.full and world > 1 and do_bwd and os.environ.get("GSPLAT_BENCH_SWEEP", "1") != "0"
     sweep_deadline = float(os.environ.get("GSPLAT_BENCH_SWEEP_DEADLINE_S", "150"))
     selftest = os.environ.get("GSPLAT_BENCH_SELFTEST", "")
 
@@ -753,75 +826,78 @@ def run_rank(args, comm, device_index):
             gc.enable()
         return status
 
-    # ---- roofline of the dominant kernel (compositing backward): HBM on algorithmic bytes, and the bound the kernel
-    # actually runs against, VALU issue (wave-level VALU instructions per launch from the SQ_INSTS_VALU pass kept in
-    # profiles/traffic.json, divided by the launch duration measured live above)
-    alg_bytes = (76 * S_eff + 20 * P) if do_bwd else (40 * S_eff + 20 * P)
-    achieved = alg_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
-    traffic = valu_insts = valu_busy = None
-    counters, profile_note = profiled_counters(args.workload)
-    if counters:
-        traffic, valu_insts, valu_busy = counters.get(dom), counters.get(dom + "_valu_insts"), counters.get(dom + "_valu_busy")
-    roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "algorithmic_bytes": alg_bytes,
-                "avg_launch_ms": dom_ms}
-    if profile_note:
-        roofline["note"] = profile_note
-    roofline_valu = None
-    if valu_insts and dom_ms > 0:
-        ginst = valu_insts / (dom_ms * 1e-3) / 1e9
-        # r03 slope experiment (profiles/r03_valu_slope.txt, tools/experiments/r03_valu_slope.sh): k extra independent
-        # v_fma_f32 per trip of render_bwd's loop cost +3.51 us per instruction (k = 4, 8, 16: +16.4, +29.8, +56.2 us on
-        # 339.8 us), i.e. 3.61 M wave trips / 1024 SIMDs x 2.2 cycles at the kernel's 2.23 GHz: the FULL nominal issue
-        # cost of the guide's table (2 cycles per wave64 VALU instruction per SIMD) plus a tenth -- nothing of an added
-        # instruction hides, so the loop is issue bound; removing the 22-instruction row reduction and its LDS atomic took
-        # -134 us = 3.9 cycles per instruction (DPP operands, selects).  frac_at_measured_issue_cost prices every VALU
-        # instruction of the launch at the measured plain cost (a lower bound: DPP / transcendental / 64-bit cost more).
-        cyc_plain, clock_ghz, simds = 2.2, 2.23, 1024
-        busy_ms = valu_insts * cyc_plain / simds / (clock_ghz * 1e6)
-        roofline_valu = {"kernel": dom, "bound": "valu_issue", "achieved": ginst, "peak": VALU_PEAK_GINST,
-                         "unit": "G wave-instructions/s", "frac": ginst / VALU_PEAK_GINST,
-                         "valu_instructions_per_launch": valu_insts,
-                         "measured_issue_cost": {"plain_valu_cycles_per_instruction_per_simd": cyc_plain,
-                                                 "row_reduction_block_cycles_per_instruction": 3.9,
-                                                 "note_r04": "measured on r03's loop (51 VALU per trip, 22 of them the row "
-                                                             "reduction); r04's loop has 39 (14 + the atomic's address): "
-                                                             "profiles/r04_ab_carried_dot_and_rows_reduction.txt",
-                                                 "wave_trips_per_launch": 3606560,
-                                                 "kernel_clock_ghz": clock_ghz,
-                                                 "source": "profiles/r03_valu_slope.txt (same-box A/B, 300 steps, two rounds)"},
-                         "frac_at_measured_issue_cost": busy_ms / dom_ms,
-                         "note": "achieved = SQ_INSTS_VALU per launch (profiles/traffic.json, same sources) / live launch "
-                                 "duration; peak = 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 v_fma_f32 "
-                                 "(MI355X_MICROARCH.md); frac_at_measured_issue_cost = instructions x 2.2 cycles / "
-                                 "(1024 SIMDs x 2.23 GHz x launch duration), every instruction at the plain-FMA cost "
-                                 "the slope experiment measured"}
+    # ---- what --full adds behind the timed region: rooflines, render rates, training steps, side workloads, baselines
+    roofline = roofline_valu = fps = fps_render_only = None
+    if args.full:
+        # ---- roofline of the dominant kernel (compositing backward): HBM on algorithmic bytes, and the bound the kernel
+        # actually runs against, VALU issue (wave-level VALU instructions per launch from the SQ_INSTS_VALU pass kept in
+        # profiles/traffic.json, divided by the launch duration measured live above)
+        alg_bytes = (76 * S_eff + 20 * P) if do_bwd else (40 * S_eff + 20 * P)
+        achieved = alg_bytes / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        traffic = valu_insts = valu_busy = None
+        counters, profile_note = profiled_counters(args.workload)
+        if counters:
+            traffic, valu_insts, valu_busy = counters.get(dom), counters.get(dom + "_valu_insts"), counters.get(dom + "_valu_busy")
+        roofline = {"kernel": dom, "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "algorithmic_bytes": alg_bytes,
+                    "avg_launch_ms": dom_ms}
+        if profile_note:
+            roofline["note"] = profile_note
+        roofline_valu = None
+        if valu_insts and dom_ms > 0:
+            ginst = valu_insts / (dom_ms * 1e-3) / 1e9
+            # r03 slope experiment (profiles/r03_valu_slope.txt, tools/experiments/r03_valu_slope.sh): k extra independent
+            # v_fma_f32 per trip of render_bwd's loop cost +3.51 us per instruction (k = 4, 8, 16: +16.4, +29.8, +56.2 us on
+            # 339.8 us), i.e. 3.61 M wave trips / 1024 SIMDs x 2.2 cycles at the kernel's 2.23 GHz: the FULL nominal issue
+            # cost of the CDNA4 issue table (2 cycles per wave64 VALU instruction per SIMD) plus a tenth -- nothing of an added
+            # instruction hides, so the loop is issue bound; removing the 22-instruction row reduction and its LDS atomic took
+            # -134 us = 3.9 cycles per instruction (DPP operands, selects).  frac_at_measured_issue_cost prices every VALU
+            # instruction of the launch at the measured plain cost (a lower bound: DPP / transcendental / 64-bit cost more).
+            cyc_plain, clock_ghz, simds = 2.2, 2.23, 1024
+            busy_ms = valu_insts * cyc_plain / simds / (clock_ghz * 1e6)
+            roofline_valu = {"kernel": dom, "bound": "valu_issue", "achieved": ginst, "peak": VALU_PEAK_GINST,
+                             "unit": "G wave-instructions/s", "frac": ginst / VALU_PEAK_GINST,
+                             "valu_instructions_per_launch": valu_insts,
+                             "measured_issue_cost": {"plain_valu_cycles_per_instruction_per_simd": cyc_plain,
+                                                     "row_reduction_block_cycles_per_instruction": 3.9,
+                                                     "note_r04": "measured on r03's loop (51 VALU per trip, 22 of them the row "
+                                                                 "reduction); r04's loop has 39 (14 + the atomic's address): "
+                                                                 "profiles/r04_ab_carried_dot_and_rows_reduction.txt",
+                                                     "wave_trips_per_launch": 3606560,
+                                                     "kernel_clock_ghz": clock_ghz,
+                                                     "source": "profiles/r03_valu_slope.txt (same-box A/B, 300 steps, two rounds)"},
+                             "frac_at_measured_issue_cost": busy_ms / dom_ms,
+                             "note": "achieved = SQ_INSTS_VALU per launch (profiles/traffic.json, same sources) / live launch "
+                                     "duration; peak = 1024 SIMDs x 2.4 GHz / 2 cycles per wave64 v_fma_f32 "
+                                     "(CDNA4 issue table); frac_at_measured_issue_cost = instructions x 2.2 cycles / "
+                                     "(1024 SIMDs x 2.23 GHz x launch duration), every instruction at the plain-FMA cost "
+                                     "the slope experiment measured"}
 
-    # ---- forward-only rate (render fps), outside the timed region
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    reps = max(5, min(args.steps, 30))
-    for _ in range(reps):
-        step.ctx.rasterize_image(dp, dc, cfg, cfg["bg"], L)
-    torch.cuda.synchronize()
-    fps = reps / (time.perf_counter() - t1)
-    # the same in a render-only context (serving: nothing kept for a backward)
-    step.ctx.set_render_only(True)
-    reps_ro = max(5, min(args.steps, 100))
-    for _ in range(5):
-        step.ctx.rasterize_image(dp, dc, cfg, cfg["bg"], L)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(reps_ro):
-        step.ctx.rasterize_image(dp, dc, cfg, cfg["bg"], L)
-    torch.cuda.synchronize()
-    fps_render_only = reps_ro / (time.perf_counter() - t1)
-    step.ctx.set_render_only(False)
+        # ---- forward-only rate (render fps), outside the timed region
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        reps = max(5, min(args.steps, 30))
+        for _ in range(reps):
+            step.ctx.rasterize_image(dp, dc, cfg, cfg["bg"], L)
+        torch.cuda.synchronize()
+        fps = reps / (time.perf_counter() - t1)
+        # the same in a render-only context (serving: nothing kept for a backward)
+        step.ctx.set_render_only(True)
+        reps_ro = max(5, min(args.steps, 100))
+        for _ in range(5):
+            step.ctx.rasterize_image(dp, dc, cfg, cfg["bg"], L)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(reps_ro):
+            step.ctx.rasterize_image(dp, dc, cfg, cfg["bg"], L)
+        torch.cuda.synchronize()
+        fps_render_only = reps_ro / (time.perf_counter() - t1)
+        step.ctx.set_render_only(False)
 
     # ---- the whole training iteration (SURVEY 8f rows f1 + f2 around the path): rasterize -> fused L1+SSIM loss ->
     # backward with the uv intermediates -> masked in-place Adam; outside the timed region, last (it moves the parameters)
     train_ms = train_ms_partial = train_ms_fused = train_ms_two = None
-    if do_bwd and os.environ.get("GSPLAT_BENCH_TRAIN_STEP", "1") != "0":
+    if args.full and do_bwd and os.environ.get("GSPLAT_BENCH_TRAIN_STEP", "1") != "0":
         ops = importlib.import_module("3dgs_amd.ops")
         opt_mod = importlib.import_module("3dgs_amd.optimizer")
         dp_train = {k: v.clone() for k, v in dp.items()}
@@ -872,7 +948,7 @@ def run_rank(args, comm, device_index):
     # sort kernels queued on A's figures: a redo), view C 3 units further in (part of the scene behind it: a different
     # cull ratio, so the walk over compacted slots switches on and off).
     alternating = None
-    if world == 1 and do_bwd and args.workload == "config3" and os.environ.get("GSPLAT_BENCH_ALTERNATING", "1") != "0":
+    if args.full and world == 1 and do_bwd and args.workload == "config3" and os.environ.get("GSPLAT_BENCH_ALTERNATING", "1") != "0":
         try:
             def moved(tz):
                 cm = dict(cam)
@@ -927,7 +1003,7 @@ def run_rank(args, comm, device_index):
     # ---- the reference host's own sequence on the headline workload (a child process), before the side workloads run
     ref_host = None
     legs_default = "1" if spawning_legs_allowed() else "0"
-    if world == 1 and do_bwd and os.environ.get("GSPLAT_BENCH_REFERENCE_HOST", legs_default) != "0":
+    if args.full and world == 1 and do_bwd and os.environ.get("GSPLAT_BENCH_REFERENCE_HOST", legs_default) != "0":
         try:
             ref_host = reference_host_path(params, cam, gi, cfg, L)
         except Exception as e:  # never lose the headline line to a side measurement
@@ -935,7 +1011,7 @@ def run_rank(args, comm, device_index):
 
     # ---- non-headline workloads (extra keys): what real training views do to the per-gaussian kernels and the binning
     extra = None
-    if world == 1 and do_bwd and not args.no_extra_workloads and args.workload == "config3":
+    if args.full and world == 1 and do_bwd and not args.no_extra_workloads and args.workload == "config3":
         extra = {}
         try:  # BASELINE configs[1]: the config the metric's "render fps" is quoted on (forward only)
             extra["config2"] = config2_workload(torch, scene, raster, dev)
@@ -949,7 +1025,7 @@ def run_rank(args, comm, device_index):
     gc.enable()
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(scene, args, params, cam, gi, cfg, N, W, H, L, do_bwd)
         except Exception as e:  # never lose the measured line to the baseline leg
@@ -963,7 +1039,8 @@ def run_rank(args, comm, device_index):
     legs_default = "1" if spawning_legs_allowed() else "0"
     # the exchange's HOST cost through the real backend, one rank (a child: it needs a process group of its own)
     host_cost = None
-    if world == 1 and do_bwd and args.workload == "config3" and os.environ.get("GSPLAT_BENCH_EXCHANGE_HOST_COST", legs_default) != "0":
+    if (args.full and world == 1 and do_bwd and args.workload == "config3"
+            and os.environ.get("GSPLAT_BENCH_EXCHANGE_HOST_COST", legs_default) != "0"):
         try:
             with socket.socket() as sk:
                 sk.bind(("127.0.0.1", 0))
@@ -997,61 +1074,64 @@ def run_rank(args, comm, device_index):
                                        "(cuda/raster.cu:12-136); the step of a host of the fused backward, which needs "
                                        "none of Sigma / J / conic / SH colour: ms_per_step_lean_forward"),
                    "M": M, "S": S, "S_eff": S_eff, "num_pairs": num_pairs, "scene_seed": scene.SEED},
-        # (multi-GPU: filled in by the payload sweep BEHIND the timed region -- every payload's ms per step, MAX over the
-        # ranks, measured on a communicator of its own; the headline ran config.exchange)
-        "exchange_ms_per_step": None,
         # what the collectives run on -- the world size as the backend's group sees it, the RCCL algorithm / protocol
         # overrides in effect -- and, for N > 1, the split exchange's two collectives timed each ALONE behind the timed
         # region (all-reduce of common[N,12], all-gather of g_rgb[N+1,3] per rank; ms, MAX over ranks): to be read against
-        # exchange_model.  null where there is nothing to measure (N = 1).
+        # exchange_model.  null where there is nothing to measure (N = 1) or nothing was measured (a run without --full).
         "collectives": dict(gdist.collective_environment(comm if world > 1 else None), all_reduce_common_ms=None,
                             all_gather_rgb_ms=None),
-        # tools/nccl_one_rank.py: every payload through RCCL with ONE rank (collectives = copies): ms per step with the
-        # exchange, and the microseconds of it the host spends in the exchange's Python + torch.distributed calls
-        "exchange_host_cost_one_rank": host_cost,
-        # what the exchange of this workload moves and costs on xGMI by the link arithmetic of 3dgs_amd/dist.py
-        # exchange_model (ring / direct bounds per collective), for the payload in use at this world size and for the
-        # 8-rank shape; the driver's measured multi-GPU step times can be checked against it
-        "exchange_model": ({"this_run": gdist.exchange_model(world, N, L, "split_direct" if step.direct else step.exchange,
-                                                             chunks=step.chunks)} if world > 1 else {})
-        | {f"{p}_at_8_ranks": gdist.exchange_model(8, N, L, p) for p in ("full", "factored", "split", "split_direct")},
-        "render_fps_forward_only": fps, "render_fps_render_only_context": fps_render_only,
-        # (the Trainer's choreography: since r06 the small groups' steps inside the per-gaussian backward, the SH and the
-        # position group behind it -- the same number as train_step_ms_small_groups_inside_the_backward below)
-        "train_step_ms_with_loss_and_adam": train_ms_partial,
-        # backward -> stored gradients -> the two optimizer kernels (the Trainer's choreography of r01-r05)
-        "train_step_ms_optimizer_kernels_behind_the_backward": train_ms,
-        # r06: the same iteration with the WHOLE optimizer step inside the per-gaussian backward (gsplat_backward_gaussians_adam
-        # mode 0, Trainer under GSPLAT_FUSED_ADAM=2): bit-identical results, one kernel instead of three -- and no faster
-        "train_step_ms_adam_inside_the_backward": train_ms_fused,
-        # ... and with band 0 / opacity / scale / rotation + the statistics inside the backward, SH and position behind it
-        "train_step_ms_small_groups_inside_the_backward": train_ms_partial,
-        # ... and as two kernels: the SH group's step in front (coefficient rows read once: update + the sums the position
-        # gradient needs), then the backward with the five small groups' steps inside (gsplat_adam_fused.mode 2)
-        "train_step_ms_sh_step_in_front_of_the_backward": train_ms_two,
         "ms_per_step_stats": step_stats,
-        "ms_per_step_full_forward_outputs": ms_other_mode if lean_headline else ms,
-        "ms_per_step_lean_forward": ms if lean_headline else ms_other_mode,
-        "ms_per_step_all_twelve_gradient_arrays": ms_all_gradients,
-        "reference_host_path": ref_host,
-        "stage_ms": {k: round(v[0], 4) for k, v in stages.items()},
-        "preprocess_ms_all_forward_outputs": round(stages_full["preprocess"][0], 4),
-        "preprocess_ms_lean_forward": round(stages_lean["preprocess"][0], 4),
-        "roofline": roofline,
-        "roofline_valu_issue": roofline_valu,
-        # the HBM-bound kernels either side of the compositing, from the per-stage pass (algorithmic bytes per
-        # gaussian: SURVEY.md 8d / DESIGN.md section 4); not the dominant kernel, reported for completeness
-        "roofline_per_gaussian_kernels": (
-            [hbm_entry("preprocess (lean)" + (": what the timed step runs" if lean_headline else ""),
-                       preprocess_bytes(M, N, L, True)[0], stages_lean["preprocess"][0], preprocess_bytes(M, N, L, True)[1]),
-             hbm_entry("preprocess (all ForwardPassData arrays stored)" + ("" if lean_headline else ": what the timed step runs"),
-                       preprocess_bytes(M, N, L, False)[0], stages_full["preprocess"][0], preprocess_bytes(M, N, L, False)[1])]
-            + ([hbm_entry("preprocess_backward", 560 * M, stages["preprocess_backward"][0])] if do_bwd else [])),
-        "alternating_views": alternating,
-        "extra_workloads": extra,
-        "cpu_baseline": cpu,
         "setup_s": round(gen_s, 1),
     }
+    if args.full:
+        line.update({
+            # (multi-GPU: filled in by the payload sweep BEHIND the timed region -- every payload's ms per step, MAX over the
+            # ranks, measured on a communicator of its own; the headline ran config.exchange)
+            "exchange_ms_per_step": None,
+            # tools/nccl_one_rank.py: every payload through RCCL with ONE rank (collectives = copies): ms per step with the
+            # exchange, and the microseconds of it the host spends in the exchange's Python + torch.distributed calls
+            "exchange_host_cost_one_rank": host_cost,
+            # what the exchange of this workload moves and costs on xGMI by the link arithmetic of 3dgs_amd/dist.py
+            # exchange_model (ring / direct bounds per collective), for the payload in use at this world size and for the
+            # 8-rank shape; measured multi-GPU step times can be checked against it
+            "exchange_model": ({"this_run": gdist.exchange_model(world, N, L, "split_direct" if step.direct else step.exchange,
+                                                                 chunks=step.chunks)} if world > 1 else {})
+            | {f"{p}_at_8_ranks": gdist.exchange_model(8, N, L, p) for p in ("full", "factored", "split", "split_direct")},
+            "render_fps_forward_only": fps, "render_fps_render_only_context": fps_render_only,
+            # (the Trainer's choreography: since r06 the small groups' steps inside the per-gaussian backward, the SH and the
+            # position group behind it -- the same number as train_step_ms_small_groups_inside_the_backward below)
+            "train_step_ms_with_loss_and_adam": train_ms_partial,
+            # backward -> stored gradients -> the two optimizer kernels (the Trainer's choreography of r01-r05)
+            "train_step_ms_optimizer_kernels_behind_the_backward": train_ms,
+            # r06: the same iteration with the WHOLE optimizer step inside the per-gaussian backward (gsplat_backward_gaussians_adam
+            # mode 0, Trainer under GSPLAT_FUSED_ADAM=2): bit-identical results, one kernel instead of three -- and no faster
+            "train_step_ms_adam_inside_the_backward": train_ms_fused,
+            # ... and with band 0 / opacity / scale / rotation + the statistics inside the backward, SH and position behind it
+            "train_step_ms_small_groups_inside_the_backward": train_ms_partial,
+            # ... and as two kernels: the SH group's step in front (coefficient rows read once: update + the sums the position
+            # gradient needs), then the backward with the five small groups' steps inside (gsplat_adam_fused.mode 2)
+            "train_step_ms_sh_step_in_front_of_the_backward": train_ms_two,
+            "ms_per_step_full_forward_outputs": ms_other_mode if lean_headline else ms,
+            "ms_per_step_lean_forward": ms if lean_headline else ms_other_mode,
+            "ms_per_step_all_twelve_gradient_arrays": ms_all_gradients,
+            "reference_host_path": ref_host,
+            "stage_ms": {k: round(v[0], 4) for k, v in stages.items()},
+            "preprocess_ms_all_forward_outputs": round(stages_full["preprocess"][0], 4),
+            "preprocess_ms_lean_forward": round(stages_lean["preprocess"][0], 4),
+            "roofline": roofline,
+            "roofline_valu_issue": roofline_valu,
+            # the HBM-bound kernels either side of the compositing, from the per-stage pass (algorithmic bytes per
+            # gaussian: SURVEY.md 8d / DESIGN.md section 4); not the dominant kernel, reported for completeness
+            "roofline_per_gaussian_kernels": (
+                [hbm_entry("preprocess (lean)" + (": what the timed step runs" if lean_headline else ""),
+                           preprocess_bytes(M, N, L, True)[0], stages_lean["preprocess"][0], preprocess_bytes(M, N, L, True)[1]),
+                 hbm_entry("preprocess (all ForwardPassData arrays stored)" + ("" if lean_headline else ": what the timed step runs"),
+                           preprocess_bytes(M, N, L, False)[0], stages_full["preprocess"][0], preprocess_bytes(M, N, L, False)[1])]
+                + ([hbm_entry("preprocess_backward", 560 * M, stages["preprocess_backward"][0])] if do_bwd else [])),
+            "alternating_views": alternating,
+            "extra_workloads": extra,
+            "cpu_baseline": cpu,
+        })
     # ---- ONE line, printed exactly once.  Multi-GPU: first the optional payload sweep, under a guard that prints the
     # line as it stands and leaves with exit code 0 if the sweep hangs; a sweep that fails is reported inside the line.
     status = "clean"

@@ -5,17 +5,17 @@ set -e
 export GSPLAT_BENCH_TRAIN_STEP=0
 export GSPLAT_BENCH_REFERENCE_HOST=0 GSPLAT_BENCH_EXCHANGE_HOST_COST=0 GSPLAT_BENCH_ALTERNATING=0   # no child processes under the profiler
 export GSPLAT_NO_BUILD=1   # the profiled process has an initialised GPU: it must not spawn make / hipcc (build before)
-OUT=${1:-gpurun_out/pmc}
+OUT=${1:?usage: bash profiles/run_pmc.sh <outdir>}
 WORKLOAD=${2:-}   # r05: empty = the bench command (headline scene); else tools/workload_stats.py <workload> (e.g. garden1200k)
-mkdir -p $OUT
+mkdir -p $OUT; OUT=$(cd "$OUT" && pwd)
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 run() { # name, counters...
   local name=$1; shift
   if [ -z "$WORKLOAD" ]; then
-    rocprofv3 --pmc "$@" --output-format csv -d $R/$OUT/$name -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extra-workloads > $R/$OUT/$name.log 2>&1 || echo "pass $name failed"
+    rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extra-workloads > $OUT/$name.log 2>&1 || echo "pass $name failed"
   else
-    rocprofv3 --pmc "$@" --output-format csv -d $R/$OUT/$name -- python3 $R/tools/workload_stats.py $WORKLOAD 6 > $R/$OUT/$name.log 2>&1 || echo "pass $name failed"
+    rocprofv3 --pmc "$@" --output-format csv -d $OUT/$name -- python3 $R/tools/workload_stats.py $WORKLOAD 6 > $OUT/$name.log 2>&1 || echo "pass $name failed"
   fi
 }
 run sq1 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU

@@ -128,3 +128,44 @@ def test_bench_line_describes_the_collectives_without_a_process_group():
     src = open(BENCH).read()
     assert '"collectives": dict(gdist.collective_environment(' in src and "all_reduce_common_ms=None" in src
     assert 'extra["config2"] = config2_workload(' in src  # BASELINE configs[1] is in the line
+
+
+def test_dump_outputs_scatter_gradients_to_global_order_and_sample_them():
+    """--dump-outputs (bench.collect_outputs) on CPU tensors shaped like a one-rank step: the compacted gradient rows go
+    back to their global gaussians (zero where culled), the sampled rows are the same in every run, every array is
+    float32 / float64, and the whole set stays under the cap even at config 3's size."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Step:
+        dev = torch.device("cpu")
+
+    N, M, H, W = 10, 4, 3, 5
+    c2g = torch.tensor([7, 1, 4, 9], dtype=torch.int32)
+    fwd = {"num_culled": M, "compact_to_global": c2g, "image": torch.rand(H, W, 3), "T": torch.rand(H, W),
+           "n": torch.randint(0, 9, (H, W), dtype=torch.int32)}
+    step = Step()
+    step.grads = {"xyz": torch.arange(N * 3, dtype=torch.float32).view(N, 3), "sh": torch.rand(N, 15, 3), "opacity": None}
+    out = bench.collect_outputs(torch, step, fwd, True, N, 1)
+    assert set(out) == {"image", "transmittance", "splats_per_pixel", "grad_xyz", "grad_sh", "grad_rows"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    assert np.array_equal(out["grad_rows"], np.arange(N))
+    want = np.zeros((N, 3), np.float32)
+    want[c2g.numpy()] = step.grads["xyz"][:M].numpy()
+    assert np.array_equal(out["grad_xyz"], want)
+    assert np.array_equal(out["splats_per_pixel"], fwd["n"].numpy().astype(np.float32))
+    # config 3: 1e6 gaussians at 1920x1080, SH 3 -- a fixed sample of rows, under 64 MB in all
+    N, M, H, W = 1_000_000, 1000, 1080, 1920
+    fwd = {"num_culled": M, "compact_to_global": torch.arange(M, dtype=torch.int32) * 997, "image": torch.zeros(H, W, 3),
+           "T": torch.zeros(H, W), "n": torch.zeros(H, W, dtype=torch.int32)}
+    step.grads = {k: torch.ones((M,) + s) for k, s in
+                  (("xyz", (3,)), ("rgb", (3,)), ("sh", (15, 3)), ("opacity", ()), ("scale", (3,)), ("quaternion", (4,)),
+                   ("precompute_rgb", (3,)))}
+    a = bench.collect_outputs(torch, step, fwd, True, N, 1)
+    b = bench.collect_outputs(torch, step, fwd, True, N, 1)
+    assert np.array_equal(a["grad_rows"], b["grad_rows"]) and len(a["grad_rows"]) == bench.DUMP_ROWS
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    picked = np.isin(a["grad_rows"], np.arange(M) * 997)
+    assert np.array_equal(a["grad_sh"][:, 0, 0] == 1.0, picked)

@@ -327,7 +327,8 @@ def _bench(world, threads, extra_env=None, steps=4):
     if threads:
         env["GSPLAT_BENCH_THREAD_RANKS"] = "1"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--workload", "small", "--steps",
-                          str(steps), "--warmup", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          str(steps), "--warmup", "2", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
+                         timeout=900)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     return out, lines, (json.loads(lines[-1]) if lines else None)
 
@@ -386,7 +387,7 @@ def test_bench_under_torch_distributed_run():
     env.update(GSPLAT_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", GSPLAT_NO_BUILD="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--workload", "small", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"],
+                          "--gpus", "2", "--workload", "small", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -394,3 +395,37 @@ def test_bench_under_torch_distributed_run():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["config"]["backend"] == "gloo" and line["value"] > 0
     assert set(line["exchange_ms_per_step"]) == SWEEP
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A run without --full: set-up, warm-up, the timed steps, the headline line (no side measurement keys), and with
+    --dump-outputs the last step's image and sampled gradients; two runs with the same arguments compute the same."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dirs = []
+    for run in range(2):
+        d = tmp_path / f"out{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "5",
+                              "--warmup", "2", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 5 and line["warmup"] == 2 and line["n_gpus"] == 1
+        assert line["ms_per_step"] > 0 and abs(line["value"] - 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in line
+        assert "stage_ms" not in line and "cpu_baseline" not in line and "extra_workloads" not in line
+        dirs.append(d)
+    names = sorted(p.name for p in dirs[0].iterdir())
+    assert names == sorted(p.name for p in dirs[1].iterdir())
+    assert {"image.npy", "grad_xyz.npy", "grad_sh.npy", "grad_rows.npy"} <= set(names)
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape
+        rel = np.linalg.norm((a - b).ravel()) / (np.linalg.norm(b.ravel()) + 1e-30)
+        assert rel < 1e-5, (n, rel)  # the same inputs: the same outputs up to the order of atomic sums
+    img = np.load(dirs[0] / "image.npy")
+    assert img.shape == (144, 256, 3) and np.isfinite(img).all() and img.std() > 0

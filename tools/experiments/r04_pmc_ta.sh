@@ -4,7 +4,7 @@ export GSPLAT_BENCH_TRAIN_STEP=0 GSPLAT_BENCH_REFERENCE_HOST=0 GSPLAT_BENCH_EXCH
 R=$GRAFT_REPO_ROOT; OUT=gpurun_out/pmc_ta; mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp
 run() { local name=$1; shift
-  timeout -k 10 150 rocprofv3 --pmc "$@" --output-format csv -d $R/$OUT/$name -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-extra-workloads > $R/$OUT/$name.log 2>&1 || echo "pass $name failed"; echo "pass $name done"; }
+  timeout -k 10 150 rocprofv3 --pmc "$@" --output-format csv -d $R/$OUT/$name -- python3 $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-extra-workloads > $R/$OUT/$name.log 2>&1 || echo "pass $name failed"; echo "pass $name done"; }
 run t1 TA_TA_BUSY_sum GRBM_GUI_ACTIVE
 run t2 TA_FLAT_READ_WAVEFRONTS_sum TA_FLAT_WRITE_WAVEFRONTS_sum
 run t3 TCP_TOTAL_ACCESSES_sum TCP_TCC_READ_REQ_sum

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 export GSPLAT_NO_BUILD=1 GSPLAT_NO_RENDER_DUMPS=1
 for rep in 1 2; do
 for tag in ${TAGS:-ai1 ai4 ai8}; do
-  GSPLAT_LIB=tools/ab/lib$tag.so timeout -k 10 300 python bench.py --steps 100 --warmup 30 --no-cpu-baseline --no-extra-workloads 2>/dev/null | python -c "
+  GSPLAT_LIB=tools/ab/lib$tag.so timeout -k 10 300 python bench.py --full --steps 100 --warmup 30 --no-cpu-baseline --no-extra-workloads 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$tag', round(d['value'],1), 'train step with loss and adam', round(d['train_step_ms_with_loss_and_adam'],4))" || exit 1
 done

@@ -10,7 +10,7 @@ for gate in ${GATES:-1e9 0 3}; do
   grep -E "stages|training done" /tmp/train_$gate.log | tail -2 | cut -c1-300
 done
 for gate in ${GATES:-1e9 0 3}; do
-  GSPLAT_FWD_SEGMENTS_GATE=$gate timeout -k 10 400 python bench.py --steps ${STEPS:-60} --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
+  GSPLAT_FWD_SEGMENTS_GATE=$gate timeout -k 10 400 python bench.py --full --steps ${STEPS:-60} --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms']; e=d['extra_workloads']
 print('gate $gate', round(d['value'],1), 'fwd', s['render_forward'], 'bwd', s['render_backward'], '|', ' '.join('%s %.4f f %.4f b %.4f' % (k, v['ms_per_step'], v['stage_ms']['render_forward'], v['stage_ms']['render_backward']) for k, v in e.items()))" || exit 1

@@ -13,7 +13,7 @@ done
 done
 for rep in 1 2; do
 for mode in 1 0; do
-  GSPLAT_NO_FWD_SEGMENTS=$mode timeout -k 10 400 python bench.py --steps ${STEPS:-100} --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
+  GSPLAT_NO_FWD_SEGMENTS=$mode timeout -k 10 400 python bench.py --full --steps ${STEPS:-100} --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['stage_ms']; e=d['extra_workloads']
 print('NO_FWD_SEGMENTS=$mode', round(d['value'],1), 'fwd', s['render_forward'], 'bwd', s['render_backward'], '|', ' '.join('%s %.4f f %.4f b %.4f' % (k, v['ms_per_step'], v['stage_ms']['render_forward'], v['stage_ms']['render_backward']) for k, v in e.items()))" || exit 1
