@@ -127,7 +127,7 @@ class AdamGroup(ctypes.Structure):  # gsplat_adam_group
 
 
 MAX_ADAM_GROUPS = 8
-ABI_VERSION = 8  # GSPLAT_ABI_VERSION of include/gsplat_hip.h; bumped with every signature change
+ABI_VERSION = 9  # GSPLAT_ABI_VERSION of include/gsplat_hip.h; bumped with every signature change
 
 # every symbol include/gsplat_hip.h declares, with its argument types
 _P, _I, _F, _S = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
@@ -205,6 +205,11 @@ SIGNATURES = {
                                             ctypes.POINTER(AdamFused), ctypes.POINTER(Gradients), _P]),
     "gsplat_context_set_render_only": (_I, [_P, _I]),
     "gsplat_context_set_lean_forward": (_I, [_P, _I]),
+    "gsplat_context_set_depth": (_I, [_P, _I]),
+    "gsplat_context_depth_map": (_I, [_P, ctypes.POINTER(_P)]),
+    "gsplat_backward_render_depth": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _P]),
+    "gsplat_backward_pass_depth": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _P, _P, _P, _F, _I,
+                                        ctypes.POINTER(Gradients), _P]),
     "gsplat_context_set_preprocess_split": (_I, [_P, _I]),
     "gsplat_context_get_counters": (_I, [_P, ctypes.POINTER(ctypes.c_longlong), _I]),
     "gsplat_context_set_timing": (_I, [_P, _I]),

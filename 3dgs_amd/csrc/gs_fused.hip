@@ -51,13 +51,14 @@ struct RawSplats;
 int launch_render_fwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, int width,
                       int height, float bg, int *n_out, float *T_out, float *image, hipStream_t st, float4 *zero, long long zero_vec,
                       unsigned short *masks_out, const int *order, int *tops_out, const TileSegments *segments,
-                      const FwdSegments *fwd_segments);
+                      const FwdSegments *fwd_segments, const DepthMaps *depth);
 int launch_fwd_segments_table(const int *ranges, int num_tiles, const FwdSegments &fs, hipStream_t st);
 int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, const int *n_px,
                       const float *T_px, const float *grad_image, int width, int height, float bg, float *rows,
                       float *g_rgb, float *g_opacity, float *g_uv, float *g_conic, hipStream_t st,
                       const unsigned short *masks_in, hipEvent_t ev_start, hipEvent_t ev_stop, const int *order,
-                      const TileSegments *segments);
+                      const TileSegments *segments,
+                      const DepthMaps *depth);
 int launch_tile_segments(const int *ranges, const int *tops, int num_tiles, const TileSegments &seg, hipStream_t st);
 int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
 bool tile_order_supported(int num_tiles);
@@ -97,6 +98,11 @@ struct gsplat_context {
   gs::DeviceBuffer seg_first, seg_extra, seg_chk;
   // ... and for the forward (gs_render.h: FwdSegments)
   gs::DeviceBuffer fseg_first, fseg_blocks, fseg_gran, fseg_part, fseg_stop;
+  // depth mode (gsplat_context_set_depth; gs_render.h: DepthMaps): the depth map and the side arrays of the long lists
+  bool depth = false;
+  bool depth_ready = false;  // the recorded forward rendered depth_map
+  bool rows_depth = false;   // the gradient rows carry dL/dz in slot 9 (gsplat_backward_render_depth with depth gradients)
+  gs::DeviceBuffer depth_map, seg_chk_d, fseg_part_d;
   void *fseg_gran_zeroed = nullptr;  // the granule block whose tags have been cleared (a fresh block holds anything)
   size_t fseg_gran_zeroed_bytes = 0;
   unsigned int fseg_epoch = 0;
@@ -176,7 +182,8 @@ struct gsplat_context {
     const gs::DeviceBuffer *all[] = {&mask, &counters, &rank, &xyz_c_all, &uv_all, &c2g, &xyz_c, &uv, &sigma, &conic, &J,
                                      &rgb, &radius, &recs, &counts, &offsets, &grad_rows, &hitmask, &keys_a, &keys_b, &pay_a, &pay_b,
                                      &sorted, &temp, &ranges, &image, &T_px, &n_px, &blockmasks, &kept, &tile_tops, &tile_order,
-                                     &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad};
+                                     &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad,
+                                     &depth_map, &seg_chk_d, &fseg_part_d};
     size_t b = 0;
     for (auto *p : all) b += p->bytes;
     return b;
@@ -187,7 +194,8 @@ struct gsplat_context {
     gs::DeviceBuffer *all[] = {&mask, &counters, &rank, &xyz_c_all, &uv_all, &c2g, &xyz_c, &uv, &sigma, &conic, &J,
                                &rgb, &radius, &recs, &counts, &offsets, &grad_rows, &hitmask, &keys_a, &keys_b, &pay_a, &pay_b,
                                &sorted, &temp, &bin_table, &ranges, &image, &T_px, &n_px, &blockmasks, &kept, &tile_tops, &tile_order,
-                               &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad};
+                               &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad,
+                               &depth_map, &seg_chk_d, &fseg_part_d};
     for (auto *p : all) p->release();
     fseg_gran_zeroed = nullptr;
     fork.destroy();
@@ -1021,7 +1029,9 @@ struct AdamFused {
 #ifndef GS_BWD3_WAVES
 #define GS_BWD3_WAVES 3  // waves per SIMD the kAdam 3 form is compiled for (r06 A/B)
 #endif
-template <int L, int kAdam = 0>
+// kDepthRow: the rows carry dL/dz of the composited depth in slot 9 (gsplat_backward_render_depth; gs_render.h:
+// DepthMaps) -- a template flag, so that the default instantiations stay exactly what they were
+template <int L, int kAdam = 0, bool kDepthRow = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam == 3 ? GS_BWD3_WAVES : 3, 8))) void preprocess_bwd_kernel(gsplat_gaussians g, const float *__restrict__ view,
                                                                 const float *__restrict__ proj, int M,
                                                                 const int *__restrict__ c2g,
@@ -1258,6 +1268,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
   float px_, py_, pz_;
   gs::to_screen_bwd(pr, x, y, z, g_u, g_v, width, height, px_, py_, pz_);
   cxg += px_; cyg += py_; czg += pz_;
+  // depth mode: row slot 9 is dL/dz of the composited depth (render_bwd_kernel<.., kDepth>; gs_render.h: DepthMaps)
+  if constexpr (kDepthRow) czg += c.y;
   // xyz_c -> xyz
   float wx, wy, wz;
   gs::camera_space_bwd(vw, cxg, cyg, czg, wx, wy, wz);
@@ -1844,6 +1856,8 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
   c->have_forward = false;
   c->rows_ready = false;
   c->order_ready = false;
+  c->depth_ready = false;
+  c->rows_depth = false;
   gs::pool_unwatch(&c->last_mask);
   c->last_mask = nullptr;  // rank[] and compact_to_global are about to be overwritten
   {  // outputs the caller took over (gsplat_context_detach_forward_outputs) come back from the pool, at their old sizes
@@ -1860,6 +1874,15 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
   const int ntx = (W + 15) / 16, nty = (H + 15) / 16, num_tiles = ntx * nty;
   const float fx = cam->focal_x, fy = cam->focal_y;
   const float tan_fovx = (float)W / (2.0f * fx), tan_fovy = (float)H / (2.0f * fy);  // cuda/raster.cu:92-93
+  // depth mode: the compositing kernels' depth instantiations (gs_render.h: DepthMaps); z from the compacted xyz_c, which
+  // preprocess writes in every mode
+  gs::DepthMaps dmap = {};
+  if (c->depth) {
+    const int r = c->depth_map.reserve((size_t)W * H * sizeof(float), st);
+    if (r) return r;
+    dmap.xyz_c = c->xyz_c.as<float>();
+    dmap.depth = c->depth_map.as<float>();
+  }
 
   if (c->timing) {  // next timing slot; its events are >= kSlots forwards old, hence complete
     c->slot = (int)(c->fwd_calls % gsplat_context::kSlots);
@@ -2100,6 +2123,7 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
       if ((r = c->seg_first.reserve(((size_t)num_tiles + 8) * 4))) return r;
       if ((r = c->seg_extra.reserve((want + 2) * sizeof(int2)))) return r;  // [want]: the count
       if ((r = c->seg_chk.reserve(slots * 256 * sizeof(float4)))) return r;
+      if (c->depth && (r = c->seg_chk_d.reserve(slots * 256 * sizeof(float)))) return r;
       seg = {c->seg_first.as<int>(), c->seg_extra.as<int2>(), reinterpret_cast<int *>(c->seg_extra.as<int2>() + want),
              c->seg_chk.as<float4>(), c->image.as<float>(), (int)want, d_slot + 2, nullptr, my_tag};
     }
@@ -2123,6 +2147,7 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
       if ((r = c->fseg_blocks.reserve((want + 2) * sizeof(int2)))) return r;  // [want]: the count
       if ((r = c->fseg_gran.reserve(2 * want * 256 * sizeof(unsigned long long)))) return r;  // t products | final Ts
       if ((r = c->fseg_part.reserve(want * 256 * sizeof(float4)))) return r;
+      if (c->depth && (r = c->fseg_part_d.reserve(want * 256 * sizeof(float)))) return r;
       if ((r = c->fseg_stop.reserve(want * 256 * sizeof(int)))) return r;
       if (c->fseg_gran.ptr != c->fseg_gran_zeroed || c->fseg_gran.bytes != c->fseg_gran_zeroed_bytes) {
         GS_HIP(hipMemsetAsync(c->fseg_gran.ptr, 0, c->fseg_gran.bytes, st));  // tags of no epoch
@@ -2138,12 +2163,17 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
       segmented_this_forward = true;  // (counted once per forward below: a redone tail comes through here twice)
     }
     if (join_pending) GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));  // (late join: the records' colour is first read here)
+    gs::DepthMaps dm = dmap;
+    if (c->depth) {
+      dm.chk = split ? c->seg_chk_d.as<float>() : nullptr;
+      dm.part = fsplit ? c->fseg_part_d.as<float>() : nullptr;
+    }
     r = gs::launch_render_fwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(), W, H, bg_color,
                               c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
                               c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)N * 4,  // M <= N is not known here yet
                               ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr,
                               (ordered || split || figures) ? c->tile_tops.as<int>() : nullptr, split ? &seg : nullptr,
-                              fsplit ? &fs : nullptr);
+                              fsplit ? &fs : nullptr, c->depth ? &dm : nullptr);
     if (r) return r;
     c->seg_ready = split;
     c->seg_cap = seg.extra_cap;
@@ -2237,7 +2267,7 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
                                c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
                                c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)M * 4,
                                ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr,
-                               ordered ? c->tile_tops.as<int>() : nullptr, nullptr, nullptr);
+                               ordered ? c->tile_tops.as<int>() : nullptr, nullptr, nullptr, c->depth ? &dmap : nullptr);
     if (rc) return rc;
     c->seg_ready = false;
     c->mark(4, true, st);
@@ -2250,6 +2280,7 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
   gs::pool_watch(c->last_mask, &c->last_mask);  // cleared when whoever ends up owning the block returns it to the pool
   c->tan_fovx = tan_fovx; c->tan_fovy = tan_fovy; c->mh_dist = cfg->mh_dist;
   c->have_forward = !ro;  // a render-only forward leaves nothing for a backward
+  c->depth_ready = c->depth;
   if (out) {
     out->num_culled = (size_t)M; out->num_pairs = (size_t)pairs; out->num_splats = S;
     out->mask = c->mask.as<unsigned char>();
@@ -2298,6 +2329,13 @@ int gsplat_backward_render(gsplat_context *c, const float *grad_image, float bg_
 
 int gsplat_backward_render_split(gsplat_context *c, const float *grad_image, float bg_color, float *rgb_global,
                                  float *common, float *uv_norm, void *stream) {
+  return gsplat_backward_render_depth(c, grad_image, nullptr, nullptr, bg_color, rgb_global, common, uv_norm, stream);
+}
+
+int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, const float *grad_depth,
+                                 const float *grad_alpha, float bg_color, float *rgb_global, float *common, float *uv_norm,
+                                 void *stream) {
+  // (every check before the first launch: a refused call leaves the context and the caller's arrays as they were)
   GS_REQUIRE(c != nullptr, "null context");
   GS_REQUIRE(c->have_forward, "no forward pass recorded in this context");
   GS_REQUIRE_DEV(grad_image);
@@ -2308,9 +2346,14 @@ int gsplat_backward_render_split(gsplat_context *c, const float *grad_image, flo
     GS_REQUIRE(((uintptr_t)common & 15) == 0, "common must be 16-byte aligned");
   }
   if (uv_norm) { GS_REQUIRE(common != nullptr, "uv_norm goes with common"); GS_REQUIRE_DEV(uv_norm); }
+  const bool depth = grad_depth != nullptr || grad_alpha != nullptr;  // both NULL: the plain backward, exactly
+  if (grad_depth) GS_REQUIRE_DEV(grad_depth);
+  if (grad_alpha) GS_REQUIRE_DEV(grad_alpha);
+  GS_REQUIRE(!depth || c->depth_ready, "depth / alpha gradients need a forward that rendered depth (gsplat_context_set_depth)");
   hipStream_t st = (hipStream_t)stream;
   const int M = c->M, W = c->width, H = c->height;
   c->rows_ready = false;
+  c->rows_depth = false;
   c->backward_seen = true;
   if (!c->rows_zeroed) {  // first backward of the context, or a second backward of the same forward
     c->mark(5, false, st);
@@ -2324,13 +2367,17 @@ int gsplat_backward_render_split(gsplat_context *c, const float *grad_image, flo
   if (c->seg_ready)
     seg = {c->seg_first.as<int>(), c->seg_extra.as<int2>(), reinterpret_cast<int *>(c->seg_extra.as<int2>() + c->seg_cap),
            c->seg_chk.as<float4>(), c->image.as<float>(), c->seg_cap, nullptr, nullptr, 0u};
+  gs::DepthMaps dm = {};
+  if (depth)
+    dm = {c->xyz_c.as<float>(), c->depth_map.as<float>(), nullptr, c->seg_ready ? c->seg_chk_d.as<float>() : nullptr,
+          grad_depth, grad_alpha};
   int rc = gs::launch_render_bwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(),
                                  c->n_px.as<int>(), c->T_px.as<float>(), grad_image, W, H, bg_color,
                                  c->grad_rows.as<float>(), nullptr, nullptr, nullptr, nullptr, st,
                                  c->blockmasks.as<unsigned short>(), timed ? c->ev[c->slot][12] : nullptr,
                                  timed ? c->ev[c->slot][13] : nullptr,
                                  (c->order_ready && !gs_no_tile_order()) ? c->tile_order.as<int>() : nullptr,
-                                 c->seg_ready ? &seg : nullptr);
+                                 c->seg_ready ? &seg : nullptr, depth ? &dm : nullptr);
   if (rc) return rc;
   if (c->seg_ready) c->n_segmented_backwards++;
   if (c->order_ready && !gs_no_tile_order()) c->n_ordered_backwards++;
@@ -2341,6 +2388,7 @@ int gsplat_backward_render_split(gsplat_context *c, const float *grad_image, flo
     GS_LAUNCH_CHECK();
   }
   c->rows_ready = true;
+  c->rows_depth = depth;
   return GSPLAT_OK;
 }
 
@@ -2455,28 +2503,29 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
   const dim3 grid(gs::div_up(span, kBlock)), block(kBlock);
   c->mark(7, false, st);
   static const AdamFused kNoAdam = {};  // (value-initialised: every pointer null)
-#define GS_BWD(LL)                                                                                                     \
+#define GS_BWD(LL) do { if (c->rows_depth) GS_BWD2(LL, true); else GS_BWD2(LL, false); } while (0)
+#define GS_BWD2(LL, DR)                                                                                                \
   do {                                                                                                                 \
     if (adam && adam_mode == 1)                                                                                        \
-      preprocess_bwd_kernel<LL, 1><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),              \
+      preprocess_bwd_kernel<LL, 1, DR><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),              \
                                                     c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx, \
                                                     tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist,                  \
                                                     cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo,          \
                                                     ranged, first_gaussian, end_gaussian, *adam);                      \
     else if (adam && adam_mode == 3)                                                                                   \
-      preprocess_bwd_kernel<LL, 3><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),              \
+      preprocess_bwd_kernel<LL, 3, DR><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),              \
                                                     c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx, \
                                                     tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist,                  \
                                                     cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo,          \
                                                     ranged, first_gaussian, end_gaussian, *adam);                      \
     else if (adam)                                                                                                     \
-      preprocess_bwd_kernel<LL, 2><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),           \
+      preprocess_bwd_kernel<LL, 2, DR><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),           \
                                                     c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx, \
                                                     tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist,                  \
                                                     cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo,          \
                                                     ranged, first_gaussian, end_gaussian, *adam);                      \
     else                                                                                                               \
-      preprocess_bwd_kernel<LL, 0><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),          \
+      preprocess_bwd_kernel<LL, 0, DR><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),          \
                                                     c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx, \
                                                     tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist,                  \
                                                     cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo,          \
@@ -2489,6 +2538,7 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
     default: GS_BWD(3); break;
   }
 #undef GS_BWD
+#undef GS_BWD2
   GS_LAUNCH_CHECK();
   c->mark(7, true, st);
   return GSPLAT_OK;
@@ -2507,6 +2557,36 @@ int gsplat_backward_pass(gsplat_context *c, const gsplat_gaussians *g, const gsp
   int rc = gsplat_backward_render(c, grad_image, bg_color, nullptr, stream);
   if (rc) return rc;
   return gsplat_backward_gaussians(c, g, cam, l_max, out, stream);
+}
+
+int gsplat_backward_pass_depth(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                               const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
+                               int l_max, const gsplat_gradients *out, void *stream) {
+  GS_REQUIRE(c && g && cam && out, "null argument struct");
+  GS_REQUIRE(c->have_forward, "no forward pass recorded in this context");
+  GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
+             "backward arguments do not match the recorded forward pass");
+  GS_REQUIRE_DEV(out->grad_xyz); GS_REQUIRE_DEV(out->grad_rgb); GS_REQUIRE_DEV(out->grad_opacity);
+  GS_REQUIRE_DEV(out->grad_scale); GS_REQUIRE_DEV(out->grad_quaternion);
+  GS_REQUIRE(((uintptr_t)out->grad_quaternion & 15) == 0, "grad_quaternion must be 16-byte aligned");
+  if (l_max > 0 && out->grad_sh) GS_REQUIRE_DEV(out->grad_sh);
+  int rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, nullptr, nullptr, nullptr, stream);
+  if (rc) return rc;
+  return gsplat_backward_gaussians(c, g, cam, l_max, out, stream);
+}
+
+int gsplat_context_set_depth(gsplat_context *c, int enabled) {
+  GS_REQUIRE(c != nullptr, "null context");
+  c->depth = enabled != 0;
+  return GSPLAT_OK;
+}
+
+int gsplat_context_depth_map(gsplat_context *c, const float **depth) {
+  GS_REQUIRE(c && depth, "null argument");
+  *depth = nullptr;
+  GS_REQUIRE(c->n_forwards > 0 && c->depth_ready, "the last forward did not render depth (gsplat_context_set_depth)");
+  *depth = c->depth_map.as<float>();
+  return GSPLAT_OK;
 }
 
 int gsplat_context_set_binning_route(gsplat_context *c, int route) {

@@ -376,13 +376,22 @@ __device__ __host__ __forceinline__ int row_moments9q_index(int lane) {
 // atomic that follows (addr = off * 5 + acc_lane), which the loop needs anyway.
 struct RowsWeights { float a[4], b[4], q; };
 
-__device__ __forceinline__ RowsWeights make_rows_weights(int lane, float cx, float cy, float g0, float g1, float g2) {
+// kFourth: the quad's fourth lane weighs aT with g3 instead of 0 -- depth mode (DepthMaps, below) passes dL/d depth, and
+// lane 3 of the row ends with a tenth total, sum aT x dL/d depth, at no extra instruction in the loop.  (A template, not
+// a defaulted argument: with g3 = 0 as an argument the default kernels' register allocation changed, 2 -> 19 spills.)
+template <bool kFourth = false>
+__device__ __forceinline__ RowsWeights make_rows_weights(int lane, float cx, float cy, float g0, float g1, float g2,
+                                                         float g3 = 0.0f) {
   const int p = lane & 3;
   RowsWeights w;
   auto qp = [](float v, auto ctrl) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), decltype(ctrl)::value, 0xF, 0xF, false));
   };
-  auto offer = [&](int k) { const int ch = p ^ k; return ch == 0 ? g0 : ch == 1 ? g1 : ch == 2 ? g2 : 0.0f; };
+  auto offer = [&](int k) {
+    const int ch = p ^ k;
+    if constexpr (kFourth) return ch == 0 ? g0 : ch == 1 ? g1 : ch == 2 ? g2 : g3;
+    else return ch == 0 ? g0 : ch == 1 ? g1 : ch == 2 ? g2 : 0.0f;
+  };
   w.a[0] = offer(0);
   w.a[1] = qp(offer(1), std::integral_constant<int, 0xB1>{});  // quad_perm [1,0,3,2]
   w.a[2] = qp(offer(2), std::integral_constant<int, 0x4E>{});  // quad_perm [2,3,0,1]
@@ -534,5 +543,22 @@ struct FwdSegments {
 // resident (the dispatch order it relies on is an assumption) recomputes after that instead of after 4 ms (r05: 4096),
 // and every such block is counted (gsplat_context_get_counters out[9]).
 constexpr int kFwdPollBudget = 128, kFwdThinLayerDefault = 512;  // (gsplat_context_set_segment_options changes them)
+
+// Depth mode (gsplat_context_set_depth): the packed compositing kernels' <.., kDepth = true> instantiations carry one more
+// "colour channel", the camera-space depth z of every gaussian, composited over a background of 0:
+//   depth(p) = sum_{i < n(p)} alpha_i T_i z_i        (alpha(p) = 1 - T(p) needs nothing of its own)
+// The forward stages z in the slot of the LDS record its loop does not read (r1.z, the plain opacity), the backward in
+// r1.w (the footprint's hy); the global 48-byte record is unchanged.  The long-list machinery gets side arrays at the
+// slots of the colour ones: a segment's partial depth next to FwdSegments::part, the depth so far next to
+// TileSegments::chk.  The backward takes dL/d depth and dL/d alpha per pixel and adds sum aT * dL/d depth (= dL/d z) as
+// the tenth value of the gaussian's gradient row (slot 9), which preprocess_bwd_kernel adds to dL/d z_c.
+struct DepthMaps {
+  const float *xyz_c;       // [M,3] compacted camera-space positions (the context's c->xyz_c)
+  float *depth;             // [H,W] the forward writes it; the backward reads it at segment boundaries
+  float *part;              // [FwdSegments::cap][256] a segment's partial depth (its own entries only)
+  float *chk;               // [TileSegments slots][256] the depth accumulated in front of a boundary
+  const float *grad_depth;  // [H,W] backward: dL/d depth (null: zero)
+  const float *grad_alpha;  // [H,W] backward: dL/d alpha (null: zero)
+};
 
 }  // namespace gs

@@ -215,6 +215,18 @@ __device__ __forceinline__ bool resolve_prefix(const FwdSegments &fs, int rank, 
   }
 }
 
+// the forward loop's read of the record's second array: (c2, log2 opa), and in depth mode z from the slot behind them
+template <bool kDepth>
+__device__ __forceinline__ void fwd_r1(const char *r1b, int off, float2 &b, float &z) {
+  if constexpr (kDepth) {
+    const float4 q = *reinterpret_cast<const float4 *>(r1b + off);
+    b = make_float2(q.x, q.y);
+    z = q.z;
+  } else {
+    b = *reinterpret_cast<const float2 *>(r1b + off);
+  }
+}
+
 // Phase A: the product of (1 - alpha) over the entries [begin, end) of the tile's list, per pixel -- the forward's loop
 // without colour, stop test and saturation bookkeeping, the same alpha values in the same order, so that the running
 // product is bit for bit the one phase C multiplies up.  `fold`: the product segment by segment from the left,
@@ -268,12 +280,12 @@ __device__ __forceinline__ float fwd_t_product(const float4 *__restrict__ recs, 
 }
 
 // One segment of a long list (gs_render.h: FwdSegments).
-template <bool kPacked>
+template <bool kPacked, bool kDepth>
 __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ recs, const RawSplats &raw,
                                                   const int *__restrict__ sorted, const int *__restrict__ ranges,
                                                   int width, int height, int ntx, unsigned short *__restrict__ masks_out,
                                                   const FwdSegments &fs, int blk, float4 *s_r0, float4 *s_r1,
-                                                  float4 *s_r2, unsigned short *s_list) {
+                                                  float4 *s_r2, unsigned short *s_list, const DepthMaps &dm) {
   const int2 bk = fs.blocks[blk];
   const int tile = bk.x, k = bk.y & 0xFFFF;
   const bool side_by_side = (bk.y >> 30) != 0;  // a thin layer (fwd_segments_table_kernel)
@@ -311,6 +323,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
       if (__syncthreads_and(!inside || f < kTMin ? 1 : 0)) {
         if (k < m - 1) granule_store(gran_f, fs.epoch, 0.0f);
         *part = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if constexpr (kDepth) dm.part[(size_t)blk * 256 + tid] = 0.0f;
         *stop = -2;
         return;
       }
@@ -334,7 +347,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
   const char *r0b = reinterpret_cast<const char *>(s_r0), *r1b = reinterpret_cast<const char *>(s_r1);
   const char *r2b = reinterpret_cast<const char *>(s_r2);
   const bool alive = inside && prefix >= kTMin;
-  float tl = alive ? 1.0f : 0.0f, T = alive ? prefix : 0.0f, T_fin = -1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
+  float tl = alive ? 1.0f : 0.0f, T = alive ? prefix : 0.0f, T_fin = -1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, ad = 0.0f;
   int n = -1;
   unsigned long long satmask = __ballot(!alive);
   int live = satmask != ~0ull ? 1 : 0;
@@ -351,6 +364,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
       stage_record(s);
       s.r1.w = __uint_as_float(hits);
       s.r2.w = s.r1.y > kLog2AlphaMax ? kLog2AlphaMax : s.r1.y;
+      if constexpr (kDepth) s.r1.z = dm.xyz_c[3 * g + 2];  // (gs_render.h: DepthMaps)
       s_r0[t] = s.r0; s_r1[t] = s.r1; s_r2[t] = s.r2;
     }
     __syncthreads();
@@ -370,9 +384,11 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
         asm volatile("ds_read_u16 %0, %2\n\tds_read_u16 %1, %2 offset:2\n\ts_waitcnt lgkmcnt(0)"
                      : "=&v"(off0), "=&v"(off1) : "v"(list_lds + 2 * i) : "memory");
         const float4 a0 = *reinterpret_cast<const float4 *>(r0b + off0), c0 = *reinterpret_cast<const float4 *>(r2b + off0);
-        const float2 b0 = *reinterpret_cast<const float2 *>(r1b + off0);
         const float4 a1 = *reinterpret_cast<const float4 *>(r0b + off1), c1 = *reinterpret_cast<const float4 *>(r2b + off1);
-        const float2 b1 = *reinterpret_cast<const float2 *>(r1b + off1);
+        float2 b0, b1;
+        float z0 = 0.0f, z1 = 0.0f;
+        fwd_r1<kDepth>(r1b, off0, b0, z0);
+        fwd_r1<kDepth>(r1b, off1, b1, z1);
         float al0 = staged_alpha_capped(a0.z, a0.w, b0.x, b0.y, c0.w, a0.x - fpx, a0.y - fpy);
         float al1 = staged_alpha_capped(a1.z, a1.w, b1.x, b1.y, c1.w, a1.x - fpx, a1.y - fpy);
         al0 = al0 > kAlphaMin ? al0 : 0.0f;
@@ -385,6 +401,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
         ar = __builtin_fmaf(c0.x, w0, ar);
         ag = __builtin_fmaf(c0.y, w0, ag);
         ab = __builtin_fmaf(c0.z, w0, ab);
+        if constexpr (kDepth) ad = __builtin_fmaf(z0, w0, ad);
         const unsigned long long s0 = __ballot(tT0 < kTMin);
         tl = tl0;
         T = tT0;
@@ -399,6 +416,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
         ar = __builtin_fmaf(c1.x, w1, ar);
         ag = __builtin_fmaf(c1.y, w1, ag);
         ab = __builtin_fmaf(c1.z, w1, ab);
+        if constexpr (kDepth) ad = __builtin_fmaf(z1, w1, ad);
         const unsigned long long s1 = __ballot(tT1 < kTMin);
         tl = tl1;
         T = tT1;
@@ -417,13 +435,14 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
   // what the segment leaves behind: T in front of the next one (0 for a pixel that stopped or was dead: dead from here on)
   if (k < m - 1) granule_store(gran_f, fs.epoch, T);
   *part = make_float4(ar, ag, ab, T_fin >= 0.0f ? T_fin : T);
+  if constexpr (kDepth) dm.part[(size_t)blk * 256 + tid] = ad;
   *stop = T_fin >= 0.0f ? n : (alive ? -1 : -2);
 }
 
 #ifndef GS_FWD_WAVES
 #define GS_FWD_WAVES 8
 #endif
-template <bool kPacked>
+template <bool kPacked, bool kDepth = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVES, 8))) void render_fwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
                                                               const int *__restrict__ sorted,
                                                               const int *__restrict__ ranges, int width, int height,
@@ -432,7 +451,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
                                                               float *__restrict__ image, float4 *__restrict__ zero,
                                                               long long zero_vec, unsigned short *__restrict__ masks_out,
                                                               const int *__restrict__ order, int *__restrict__ tops_out,
-                                                              TileSegments seg, FwdSegments fs) {
+                                                              TileSegments seg, FwdSegments fs, DepthMaps dm) {
+  static_assert(kPacked || !kDepth, "depth mode is a mode of the context's (packed) kernels");
   __shared__ float4 s_r0[kBatch + 1], s_r1[kBatch + 1], s_r2[kBatch + 1];  // [kBatch]: the all-zero sentinel record
   __shared__ int s_tile_top;
   __shared__ __attribute__((aligned(16))) unsigned short s_list[16 * kListStride + 2];
@@ -450,7 +470,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
   if constexpr (kPacked) {
     if (segmented && (int)blockIdx.x < fs.cap) {
       if ((int)blockIdx.x < *fs.count)
-        fwd_segment_block<kPacked>(recs, raw, sorted, ranges, width, height, ntx, masks_out, fs, (int)blockIdx.x, s_r0, s_r1, s_r2, s_list);
+        fwd_segment_block<kPacked, kDepth>(recs, raw, sorted, ranges, width, height, ntx, masks_out, fs, (int)blockIdx.x, s_r0, s_r1, s_r2, s_list, dm);
       return;
     }
   }
@@ -479,7 +499,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
   const int start = ranges[tile], total = ranges[tile + 1] - start;
   // A saturated pixel keeps T = 0 in the running transmittance, so every later splat blends with weight 0 and the
   // common path needs no per-pixel "done" masking; its real final transmittance and stop index live in T_fin / n.
-  float T = inside ? 1.0f : 0.0f, T_fin = -1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f;
+  float T = inside ? 1.0f : 0.0f, T_fin = -1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, ad = 0.0f;
   int n = total;
   unsigned long long satmask = __ballot(!inside);  // lanes whose pixel is saturated or outside the image
   int live = satmask != ~0ull ? 1 : 0;
@@ -492,8 +512,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
     // rebuilt per batch instead of living in registers across the compositing loop
     int t = tid;
     asm volatile("" : "+v"(t));
-    if (checkpoints && base > 0 && base % kSegEntries == 0)  // (gs_render.h: TileSegments)
+    if (checkpoints && base > 0 && base % kSegEntries == 0) {  // (gs_render.h: TileSegments)
       seg.chk[(size_t)segment_slot(start, base / kSegEntries) * 256 + t] = make_float4(T, ar, ag, ab);
+      if constexpr (kDepth) dm.chk[(size_t)segment_slot(start, base / kSegEntries) * 256 + t] = ad;
+    }
 #if GS_STAMP
     ++st_batches;
     GS_LAP(st_lists);  // (prologue of the first batch; nothing between the batches)
@@ -518,6 +540,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
       // below 0.99f (the backward keeps its own 0.99f: it needs the uncapped value next to the capped one).  NaN stays NaN.
       s.r1.w = __uint_as_float(hits);
       s.r2.w = s.r1.y > kLog2AlphaMax ? kLog2AlphaMax : s.r1.y;
+      if constexpr (kDepth) s.r1.z = dm.xyz_c[3 * g + 2];  // (gs_render.h: DepthMaps; the loop never reads r1.z otherwise)
       s_r0[t] = s.r0; s_r1[t] = s.r1; s_r2[t] = s.r2;
     }
     GS_LAP(st_stage);
@@ -548,9 +571,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
         asm volatile("ds_read_u16 %0, %2\n\tds_read_u16 %1, %2 offset:2\n\ts_waitcnt lgkmcnt(0)"
                      : "=&v"(off0), "=&v"(off1) : "v"(list_lds + 2 * i) : "memory");
         const float4 a0 = *reinterpret_cast<const float4 *>(r0b + off0), c0 = *reinterpret_cast<const float4 *>(r2b + off0);
-        const float2 b0 = *reinterpret_cast<const float2 *>(r1b + off0);
         const float4 a1 = *reinterpret_cast<const float4 *>(r0b + off1), c1 = *reinterpret_cast<const float4 *>(r2b + off1);
-        const float2 b1 = *reinterpret_cast<const float2 *>(r1b + off1);
+        float2 b0, b1;
+        float z0 = 0.0f, z1 = 0.0f;
+        fwd_r1<kDepth>(r1b, off0, b0, z0);
+        fwd_r1<kDepth>(r1b, off1, b1, z1);
         // (c.w: the exponent's bound, so the colour reads stay 16-byte reads -- a ds_read_b96 costs twice the LDS cycles)
         float al0 = staged_alpha_capped(a0.z, a0.w, b0.x, b0.y, c0.w, a0.x - fpx, a0.y - fpy);  // <= 0.99
         float al1 = staged_alpha_capped(a1.z, a1.w, b1.x, b1.y, c1.w, a1.x - fpx, a1.y - fpy);
@@ -567,6 +592,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
         ar = __builtin_fmaf(c0.x, w0, ar);
         ag = __builtin_fmaf(c0.y, w0, ag);
         ab = __builtin_fmaf(c0.z, w0, ab);
+        if constexpr (kDepth) ad = __builtin_fmaf(z0, w0, ad);
         const unsigned long long s0 = __ballot(tT0 < kTMin);  // this splat was still accumulated (render.cu:76-87)
         T = tT0;
         if (s0 != satmask) {  // rare: some pixel saturated with the trip's first splat
@@ -582,6 +608,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
         ar = __builtin_fmaf(c1.x, w1, ar);
         ag = __builtin_fmaf(c1.y, w1, ag);
         ab = __builtin_fmaf(c1.z, w1, ab);
+        if constexpr (kDepth) ad = __builtin_fmaf(z1, w1, ad);
         const unsigned long long s1 = __ballot(tT1 < kTMin);
         T = tT1;
         if (s1 != satmask) {  // rare: ... with its second
@@ -617,6 +644,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
     image[3 * pid + 0] = ar + Tout * bg;
     image[3 * pid + 1] = ag + Tout * bg;
     image[3 * pid + 2] = ab + Tout * bg;
+    if constexpr (kDepth) dm.depth[pid] = ad;  // (background 0)
   }
 #if GS_STAMP
   if (lane == 0) {
@@ -636,8 +664,13 @@ __device__ __forceinline__ int row_max_int(int v) {  // max over the 16 lanes of
   return v;
 }
 
-template <bool kPacked, bool kRows, int kB>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void render_bwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
+// waves per SIMD the depth-mode backward is compiled for (gs_render.h: DepthMaps): at 8 it spills 38 registers in the
+// trip loop, at 7 it holds 72 VGPRs without spills
+#ifndef GS_BWD_DEPTH_WAVES
+#define GS_BWD_DEPTH_WAVES 7
+#endif
+template <bool kPacked, bool kRows, int kB, bool kDepth = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDepth ? GS_BWD_DEPTH_WAVES : 8, 8))) void render_bwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
                                                               const int *__restrict__ sorted,
                                                               const int *__restrict__ ranges,
                                                               const int *__restrict__ n_px,
@@ -645,12 +678,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                                                               const float *__restrict__ grad_image, int width,
                                                               int height, int ntx, int num_tiles, float bg,
                                                               GradOut out, const unsigned short *__restrict__ masks_in,
-                                                              const int *__restrict__ order, TileSegments seg) {
+                                                              const int *__restrict__ order, TileSegments seg,
+                                                              DepthMaps dm) {
+  static_assert(kPacked || !kDepth, "depth mode is a mode of the context's (packed) kernels");
+  static_assert(!kDepth || GS_ROWSUM_QUAD == 2, "the tenth sum rides in row_moments9r's colour register");
   __shared__ float4 s_r0[kB + 1], s_r1[kB + 1];  // [kB]: the all-zero sentinel record
   // [slot][9]: rgb, S0, Sx, Sy, Sxx, Sxy, Syy.  Doubles on purpose: on gfx950 ds_add_f32 retires about one LANE
   // every three cycles while ds_add_f64 runs at LDS rate (profiles/microbench/lds_atomic_rate: 109 vs 16 cycles for
   // a 36-lane instruction), and the merge across the tile's 16 blocks needs one atomic per trip.
-  constexpr int kAcc = 10;  // doubles per slot (nine used): 80 bytes = 5 x the list entry's byte offset
+  constexpr int kAcc = 10;  // doubles per slot (nine used, ten in depth mode): 80 bytes = 5 x the list entry's byte offset
+  constexpr int kRes = kDepth ? 10 : 9;  // gradient values per gaussian: row slots 0..8 (depth mode: and slot 9, dL/dz)
   __shared__ double s_acc[(kB + 1) * kAcc];  // slot kB: the sentinel's (rows past the end of their list add zeros there)
   __shared__ int s_id[kB];
   // row lists | third record array; both are dead once the batch's trips are done, and the flush parks the nine
@@ -659,7 +696,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   unsigned short *s_list = reinterpret_cast<unsigned short *>(s_mix);
   float4 *s_r2 = reinterpret_cast<float4 *>(s_mix + 16 * kB * 2);
   float *s_res = reinterpret_cast<float *>(s_mix);
-  static_assert(kB * 9 * 4 <= 16 * kB * 2 + kB * 16, "the flush values must not reach the sentinel record");
+  static_assert(kB * kRes * 4 <= 16 * kB * 2 + kB * 16, "the flush values must not reach the sentinel record");
   __shared__ int s_top;
   // which tile, and which segment of its list (gs_render.h: TileSegments; seg_a = 0, seg_end = -1: the whole list)
   int tile, seg_a = 0, seg_end = -1, chk_slot = -1;
@@ -704,12 +741,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   char *accb = reinterpret_cast<char *>(s_acc);
 
   int n = 0;
-  float Tf = 0.0f, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f;
+  float Tf = 0.0f, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, gD = 0.0f, gA = 0.0f;
   if (inside) {
     const int pid = py * width + px;
     n = n_px[pid];
     Tf = T_px[pid];
     g0 = grad_image[3 * pid]; g1 = grad_image[3 * pid + 1]; g2 = grad_image[3 * pid + 2];
+    if constexpr (kDepth) {
+      if (dm.grad_depth) gD = dm.grad_depth[pid];
+      if (dm.grad_alpha) gA = dm.grad_alpha[pid];
+    }
   }
   // Running transmittance, and s = (pixel gradient) . (colour behind the current splat).  The colour behind only ever
   // enters through that dot product, and its back-to-front recurrence c <- c + alpha (colour - c) is linear, so the
@@ -725,12 +766,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       const float4 ck = seg.chk[(size_t)chk_slot * 256 + tid];
       T = ck.x;
       const float inv = __builtin_amdgcn_rcpf(ck.x);
-      s = (g0 * (seg.image[3 * pid] - ck.y) + g1 * (seg.image[3 * pid + 1] - ck.z) + g2 * (seg.image[3 * pid + 2] - ck.w)) * inv;
+      if constexpr (kDepth) {
+        // depth behind the boundary: (depth image - depth so far) / T_b; alpha behind it: (T_b - T_final) / T_b
+        const float dk = dm.chk[(size_t)chk_slot * 256 + tid];
+        s = (g0 * (seg.image[3 * pid] - ck.y) + g1 * (seg.image[3 * pid + 1] - ck.z) + g2 * (seg.image[3 * pid + 2] - ck.w) +
+             gD * (dm.depth[pid] - dk) + gA * (ck.x - Tf)) * inv;
+      } else {
+        s = (g0 * (seg.image[3 * pid] - ck.y) + g1 * (seg.image[3 * pid + 1] - ck.z) + g2 * (seg.image[3 * pid + 2] - ck.w)) * inv;
+      }
       n = seg_end - seg_a;
     } else {
       n = max(n - seg_a, 0);  // it stops inside the segment or in front of it: as an unsplit list from here on
     }
   }
+  // Depth mode: two more channels, (z, 1) with pixel gradient (dL/d depth, dL/d alpha), both over a background of 0.  The
+  // alpha channel's colour is 1 for every gaussian, so its share of t = grad . (colour - colour behind) is gA - gA c_a:
+  // carried as s - gA, the recurrence s <- s + alpha t is unchanged and t gains only the depth's FMA per trip.
+  if constexpr (kDepth) s -= gA;
   const int row_top_v = row_max_int(n);
   const int rt0 = __builtin_amdgcn_readlane(row_top_v, 0), rt1 = __builtin_amdgcn_readlane(row_top_v, 16);
   const int rt2 = __builtin_amdgcn_readlane(row_top_v, 32), rt3 = __builtin_amdgcn_readlane(row_top_v, 48);
@@ -752,7 +804,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   // where this lane's share of the nine row totals goes (see row_moments9), and the lane constants of the sums:
   // pixel position relative to the tile centre, pixel gradient
 #if GS_ROWSUM_QUAD == 2
-  const int red_idx = row_moments9r_index(lane);
+  // (depth mode: lane 3 of the row holds the tenth sum, aT x dL/d depth: the fourth channel of the colour register)
+  const int red_idx = kDepth && (lane & 15) == 3 ? 9 : row_moments9r_index(lane);
 #elif GS_ROWSUM_QUAD
   const int red_idx = row_moments9q_index(lane);
 #else
@@ -772,6 +825,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
   // what waves 2 and 3 hold for the NEXT batch: slot (thread - 128)'s list entry, record and block mask
   SplatRec pre = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
   int pre_g = 0;
+  float pre_z = 0.0f;  // (depth mode)
   auto prefetch = [&](int next_base, int tt) {
     if constexpr (kSplit) {
       const int slot = tt - 128;
@@ -779,6 +833,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         pre_g = sorted[start + next_base + slot];
         pre = load_record<kPacked>(pre_g, recs, raw);
         pre.r2.w = __uint_as_float((unsigned int)masks_in[start + next_base + slot]);
+        if constexpr (kDepth) pre_z = dm.xyz_c[3 * pre_g + 2];
         // (nothing here may WAIT for these loads: converting the record in this place holds waves 2 and 3 back from the
         // barrier in front of the flush's second step -- measured +8 us, profiles/r05_ab_split_staging.txt; the values are
         // first touched at staging time, a whole flush later)
@@ -805,6 +860,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         if (slot < count) {
           SplatRec s = pre;
           stage_record(s);
+          if constexpr (kDepth) s.r1.w = pre_z;  // (the loop never reads r1.w otherwise)
           s_r0[slot] = s.r0; s_r1[slot] = s.r1; s_r2[slot] = s.r2;
           s_id[slot] = pre_g;
         }
@@ -832,6 +888,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         if constexpr (kPacked) s.r2.w = __uint_as_float((unsigned int)masks_in[start + base + t]);
         else s.r2.w = __uint_as_float(block_hits(s, tx0, ty0));
         stage_record(s);
+        if constexpr (kDepth) s.r1.w = dm.xyz_c[3 * g + 2];
         s_r0[t] = s.r0; s_r1[t] = s.r1; s_r2[t] = s.r2;
         s_id[t] = g;
       }
@@ -855,11 +912,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       // The lane constants of the nine sums (pixel position relative to the tile centre, pixel gradient) are rebuilt
       // per batch behind an opaque copy, so that they are not live across staging and flush: held for the whole
       // kernel they push it past the 80-register step and the compiler spills them to scratch (+0.2 GB of traffic).
-      float g0b = g0, g1b = g1, g2b = g2;
+      float g0b = g0, g1b = g1, g2b = g2, gDb = 0.0f;
       asm volatile("" : "+v"(g0b), "+v"(g1b), "+v"(g2b));
+      if constexpr (kDepth) {
+        gDb = gD;
+        asm volatile("" : "+v"(gDb));
+      }
 #if GS_ROWSUM_QUAD == 2
-      const RowsWeights rw = make_rows_weights(t & 63, (float)(((t >> 6) & 1) * 8 + ((t >> 4) & 1) * 4 + (t & 3)) - 7.5f,
-                                               (float)((t >> 7) * 8 + ((t >> 5) & 1) * 4 + ((t >> 2) & 3)) - 7.5f, g0b, g1b, g2b);
+      const RowsWeights rw = make_rows_weights<kDepth>(t & 63, (float)(((t >> 6) & 1) * 8 + ((t >> 4) & 1) * 4 + (t & 3)) - 7.5f,
+                                                       (float)((t >> 7) * 8 + ((t >> 5) & 1) * 4 + ((t >> 2) & 3)) - 7.5f, g0b, g1b, g2b, gDb);
 #elif GS_ROWSUM_QUAD
       // (from the opaque index, like the addresses above: derived from the plain thread index the twelve weights are
       // loop-invariant for the whole kernel, get hoisted above the batch loop and spilled)
@@ -947,7 +1008,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
           T *= inv;                                           // transmittance in front of this splat
           const float aT = alpha * T;
           // t = grad . (colour - colour behind): three FMAs on the carried dot product
-          const float t = __builtin_fmaf(c.z, g2, __builtin_fmaf(c.y, g1, t0));
+          float t = __builtin_fmaf(c.z, g2, __builtin_fmaf(c.y, g1, t0));
+          if constexpr (kDepth) t = __builtin_fmaf(b.w, gD, t);  // + z . dL/d depth (the alpha channel rides in s)
           const float ga = t * T;                             // d/d alpha (cuda/render_backward.cu:139-151)
           s = __builtin_fmaf(alpha, t, s);                    // grad . colour behind the next (nearer) splat
           const float gp = og * ga;                           // d/d power
@@ -1019,7 +1081,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       // six at once do not occur).
       const bool any_gp = (S1 != 0.0) | (Sx != 0.0) | (Sy != 0.0) | (acc[6] != 0.0) | (acc[7] != 0.0) | (acc[8] != 0.0);
       const float keep = (opa == 1.0f || !any_gp) ? 0.0f : 1.0f;
-      float *res = &s_res[t * 9];
+      float *res = &s_res[t * kRes];
       res[0] = keep * (float)acc[0];
       res[1] = keep * (float)acc[1];
       res[2] = keep * (float)acc[2];
@@ -1029,18 +1091,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       res[6] = keep * (-0.5f * syy);                                                 // conic11
       res[7] = keep * (-(ca * sx + cb * sy) * (0.5f * (float)width));                // u (render_backward.cu:180-186)
       res[8] = keep * (-(cc * sy + cb * sx) * (0.5f * (float)height));               // v (:181-187)
+      if constexpr (kDepth) res[9] = keep * (float)acc[9];                            // dL/dz = sum aT dL/d depth
     }
     GS_LAP(st_flush);
     __syncthreads();
     GS_LAP(st_bar3);
     // step 2: 16 lanes per gaussian -> each wave instruction touches four whole 64-byte rows
     const int k = t & 15;
-    if (k < 9) {
+    if (k < kRes) {
 #pragma unroll 4
       for (int r = 0; r < (kB + 15) / 16; ++r) {
         const int slot = r * 16 + (t >> 4);
         if (slot >= count) continue;
-        const float val = s_res[slot * 9 + k];
+        const float val = s_res[slot * kRes + k];
         if (!(val != 0.0f)) continue;  // zero (nothing to add) -- NaN still goes out
 #if GS_ABLATE == 3
         asm volatile("" ::"v"(val));
@@ -1656,10 +1719,12 @@ __global__ __launch_bounds__(1024) void fwd_segments_table_kernel(const int *__r
 // ... and behind it: one block per tile adds up what the tile's segment blocks left (fixed order: the same image in every
 // run), finds the segment the pixel stopped in and writes the forward's per-pixel outputs, the tile's largest stop index
 // and the backward's checkpoints {T in front of the boundary, colour in front of it} (gs_render.h: TileSegments).
+template <bool kDepth = false>
 __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__restrict__ ranges, int width, int height,
                                                                    int ntx, int num_tiles, float bg, int *__restrict__ n_out,
                                                                    float *__restrict__ T_out, float *__restrict__ image,
-                                                                   int *__restrict__ tops_out, FwdSegments fs, TileSegments seg) {
+                                                                   int *__restrict__ tops_out, FwdSegments fs, TileSegments seg,
+                                                                   DepthMaps dm) {
   __shared__ int s_top;
   const int tile = blockIdx.x;
   const int rank = fs.rank[tile];
@@ -1673,7 +1738,7 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
   const bool inside = px < width && py < height;
   const int start = ranges[tile], total = ranges[tile + 1] - start;
   const int m = (total + kSegEntries - 1) / kSegEntries;
-  float ar = 0.0f, ag = 0.0f, ab = 0.0f, Tout = 1.0f;
+  float ar = 0.0f, ag = 0.0f, ab = 0.0f, ad = 0.0f, Tout = 1.0f;  // (depth: added in the colours' order)
   int n = total;
   // kAhead segments' values are requested before the first is looked at: one at a time the longest list's twenty
   // segments were twenty dependent round trips (28 us behind the forward)
@@ -1682,13 +1747,14 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
   for (int k0 = 0; k0 < m && !done; k0 += kAhead) {
     int st[kAhead];
     float4 p[kAhead];
-    float pref[kAhead];
+    float pref[kAhead], pd[kAhead];
 #pragma unroll
     for (int q = 0; q < kAhead; ++q) {
       const int k = min(k0 + q, m - 1);
       const size_t slot = (size_t)(fs.base[k] + rank);
       st[q] = fs.stop[slot * 256 + tid];
       p[q] = fs.part[slot * 256 + tid];
+      pd[q] = kDepth ? dm.part[slot * 256 + tid] : 0.0f;
       // T in front of boundary k: what the segment in front left behind (read by the backward only for pixels that pass
       // the boundary alive, for which it is exactly the T segment k started from)
       pref[q] = k > 0 ? __uint_as_float((unsigned int)fs.granules[((size_t)fs.cap + fs.base[k - 1] + rank) * 256 + tid]) : 1.0f;
@@ -1697,9 +1763,13 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
     for (int q = 0; q < kAhead; ++q) {
       const int k = k0 + q;
       if (k >= m || done) break;
-      if (k > 0 && seg.chk) seg.chk[(size_t)segment_slot(start, k) * 256 + tid] = make_float4(pref[q], ar, ag, ab);
+      if (k > 0 && seg.chk) {
+        seg.chk[(size_t)segment_slot(start, k) * 256 + tid] = make_float4(pref[q], ar, ag, ab);
+        if constexpr (kDepth) dm.chk[(size_t)segment_slot(start, k) * 256 + tid] = ad;
+      }
       if (st[q] == -2) { done = true; break; }  // (a pixel outside the image; inside it a pixel is dead only behind the segment it stopped in)
       ar += p[q].x; ag += p[q].y; ab += p[q].z;
+      if constexpr (kDepth) ad += pd[q];
       Tout = p[q].w;
       if (st[q] >= 0) { n = st[q]; done = true; }
     }
@@ -1719,6 +1789,7 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
     image[3 * pid + 0] = ar + Tout * bg;
     image[3 * pid + 1] = ag + Tout * bg;
     image[3 * pid + 2] = ab + Tout * bg;
+    if constexpr (kDepth) dm.depth[pid] = ad;
   }
 }
 
@@ -1732,20 +1803,27 @@ int launch_fwd_segments_table(const int *ranges, int num_tiles, const FwdSegment
 int launch_render_fwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, int width,
                       int height, float bg, int *n_out, float *T_out, float *image, hipStream_t st, float4 *zero,
                       long long zero_vec, unsigned short *masks_out, const int *order, int *tops_out, const TileSegments *segments,
-                      const FwdSegments *fwd_segments) {
+                      const FwdSegments *fwd_segments, const DepthMaps *depth) {
   const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
   RawSplats none = {nullptr, nullptr, nullptr, nullptr};
   const TileSegments seg = segments ? *segments : TileSegments{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
   const FwdSegments fs = fwd_segments ? *fwd_segments : FwdSegments{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0};
   const dim3 grid(tile_grid(num_tiles) + (fs.blocks ? fs.cap : 0)), block(256);
-  if (recs) {
-    render_fwd_kernel<true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs);
+  const DepthMaps dm = depth ? *depth : DepthMaps{};
+  GS_REQUIRE(recs || !depth, "depth mode needs the packed records");
+  if (recs && depth) {
+    render_fwd_kernel<true, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm);
+  } else if (recs) {
+    render_fwd_kernel<true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm);
   } else {
-    render_fwd_kernel<false><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, nullptr, order, tops_out, seg, fs);
+    render_fwd_kernel<false><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, nullptr, order, tops_out, seg, fs, dm);
   }
   GS_LAUNCH_CHECK();
   if (fs.blocks) {
-    fwd_segments_combine_kernel<<<num_tiles, 256, 0, st>>>(ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, tops_out, fs, seg);
+    if (depth)
+      fwd_segments_combine_kernel<true><<<num_tiles, 256, 0, st>>>(ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, tops_out, fs, seg, dm);
+    else
+      fwd_segments_combine_kernel<<<num_tiles, 256, 0, st>>>(ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, tops_out, fs, seg, dm);
     GS_LAUNCH_CHECK();
   }
   return GSPLAT_OK;
@@ -1754,7 +1832,8 @@ int launch_render_fwd(const float4 *recs, const RawSplats *raw, const int *sorte
 int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, const int *n_px,
                       const float *T_px, const float *grad_image, int width, int height, float bg, float *rows,
                       float *g_rgb, float *g_opacity, float *g_uv, float *g_conic, hipStream_t st, const unsigned short *masks_in,
-                      hipEvent_t ev_start, hipEvent_t ev_stop, const int *order, const TileSegments *segments) {
+                      hipEvent_t ev_start, hipEvent_t ev_stop, const int *order, const TileSegments *segments,
+                      const DepthMaps *depth) {
   const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
   const TileSegments seg = segments ? *segments : TileSegments{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
   // split lists: their further segments are extra blocks in front of the main grid (blocks beyond the count leave at once)
@@ -1763,7 +1842,16 @@ int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorte
   GradOut out = {rows, g_rgb, g_opacity, g_uv, g_conic};
   const char *pp_env = getenv("GSPLAT_BWD_PINGPONG");  // (read per launch: the tests switch it inside one process)
   const int pingpong = pp_env ? atoi(pp_env) : GS_BWD_PINGPONG;
-  if (recs && rows && pingpong) {  // r06 experiment: two half-batches in flight (render_bwd_pp_kernel)
+  const DepthMaps dm = depth ? *depth : DepthMaps{};
+  GS_REQUIRE(!depth || (recs && rows), "depth mode needs the packed records and the gradient rows");
+  if (depth) {  // (gs_render.h: DepthMaps; the ping-pong experiment has no depth form: always the default loop)
+    if (ev_start && ev_stop)
+      hipExtLaunchKernelGGL((render_bwd_kernel<true, true, GS_BWD_BATCH, true>), grid, block, 0, st, ev_start, ev_stop, 0, recs,
+                            none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order,
+                            seg, dm);
+    else
+      render_bwd_kernel<true, true, GS_BWD_BATCH, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
+  } else if (recs && rows && pingpong) {  // r06 experiment: two half-batches in flight (render_bwd_pp_kernel)
     if (ev_start && ev_stop)
       hipExtLaunchKernelGGL(render_bwd_pp_kernel, grid, block, 0, st, ev_start, ev_stop, 0, recs, sorted, ranges, n_px, T_px,
                             grad_image, width, height, ntx, num_tiles, bg, rows, masks_in, order, seg);
@@ -1774,15 +1862,15 @@ int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorte
     // its completion signal.  Two hipEventRecord calls around the launch are barrier packets of their own and kept the
     // GPU idle for ~11 us before and ~6 us after the kernel in every step they were on.
     hipExtLaunchKernelGGL((render_bwd_kernel<true, true, GS_BWD_BATCH>), grid, block, 0, st, ev_start, ev_stop, 0, recs, none,
-                          sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg);
+                          sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
   } else if (recs && rows) {
-    render_bwd_kernel<true, true, GS_BWD_BATCH><<<grid, block, 0, st>>>(recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg);
+    render_bwd_kernel<true, true, GS_BWD_BATCH><<<grid, block, 0, st>>>(recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
   } else if (recs) {
-    render_bwd_kernel<true, false, GS_BWD_BATCH><<<grid, block, 0, st>>>(recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg);
+    render_bwd_kernel<true, false, GS_BWD_BATCH><<<grid, block, 0, st>>>(recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
   } else if (rows) {  // the reference operator's input arrays, gradient rows out (gsplat_render_image_backward stages them)
-    render_bwd_kernel<false, true, GS_BWD_BATCH><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg);
+    render_bwd_kernel<false, true, GS_BWD_BATCH><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
   } else {
-    render_bwd_kernel<false, false, GS_BWD_BATCH><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg);
+    render_bwd_kernel<false, false, GS_BWD_BATCH><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
   }
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;
@@ -1815,7 +1903,7 @@ int gsplat_render_image(const float *uv, const float *opacity, const float *coni
   gs::RawSplats raw = {uv, opacity, conic, rgb};
   return gs::launch_render_fwd(nullptr, &raw, sorted_splats, splat_range_by_tile, image_width, image_height,
                                background_opacity, splats_per_pixel, weight_per_pixel, image, (hipStream_t)stream, nullptr,
-                               0, nullptr, nullptr, nullptr, nullptr, nullptr);
+                               0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"
@@ -1895,7 +1983,7 @@ int gsplat_render_image_backward(const float *uvs, const float *opacity, const f
     GS_HIP(hipMemsetAsync(rows.ptr, 0, (size_t)bound * 64, st));
     rc = gs::launch_render_bwd(nullptr, &raw, sorted_splats, splat_range_by_tile, num_splats_per_pixel,
                                final_weight_per_pixel, grad_image, image_width, image_height, background_opacity,
-                               rows.as<float>(), nullptr, nullptr, nullptr, nullptr, st, nullptr, nullptr, nullptr, nullptr, nullptr);
+                               rows.as<float>(), nullptr, nullptr, nullptr, nullptr, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (rc) return rc;
     rows_to_arrays_kernel<<<gs::div_up(bound, 256), 256, 0, st>>>(rows.as<float4>(), bound, grad_rgb, grad_opacity, grad_uv,
                                                                   grad_conic);
@@ -1904,7 +1992,7 @@ int gsplat_render_image_backward(const float *uvs, const float *opacity, const f
   }
   return gs::launch_render_bwd(nullptr, &raw, sorted_splats, splat_range_by_tile, num_splats_per_pixel,
                                final_weight_per_pixel, grad_image, image_width, image_height, background_opacity,
-                               nullptr, grad_rgb, grad_opacity, grad_uv, grad_conic, st, nullptr, nullptr, nullptr, nullptr, nullptr);
+                               nullptr, grad_rgb, grad_opacity, grad_uv, grad_conic, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -46,15 +46,20 @@ class _LazyViews(dict):
     def __init__(self, plain, specs, owner):
         super().__init__(plain)
         self._specs, self._owner = specs, owner
+        self._derived = {}  # entries computed from the others on first use: name -> f(views) (no closure over self: a
+        # cycle would keep the views, and the context they hold, alive until the cyclic collector runs)
 
     def __missing__(self, key):
-        ptr, shape, typestr = self._specs.pop(key)  # KeyError for unknown names, as a dict
-        value = _view(ptr, shape, typestr, self._owner)
+        if key in self._derived:
+            value = self._derived.pop(key)(self)
+        else:
+            ptr, shape, typestr = self._specs.pop(key)  # KeyError for unknown names, as a dict
+            value = _view(ptr, shape, typestr, self._owner)
         self[key] = value
         return value
 
     def _all(self):
-        for key in list(self._specs):
+        for key in list(self._specs) + list(self._derived):
             self[key]
         return self
 
@@ -62,7 +67,7 @@ class _LazyViews(dict):
         return self[key] if key in self else default
 
     def __contains__(self, key):
-        return dict.__contains__(self, key) or key in self._specs
+        return dict.__contains__(self, key) or key in self._specs or key in self._derived
 
     def __iter__(self):
         return dict.__iter__(self._all())
@@ -80,8 +85,21 @@ class _LazyViews(dict):
         return dict.values(self._all())
 
 
+def _alpha(views):
+    return 1.0 - views["T"]
+
+
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def _map_ptr(t):
+    """A per-pixel gradient map ([H,W] float32, contiguous, on the device) as a pointer; None stays NULL."""
+    if t is None:
+        return None
+    if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+        raise ValueError("grad_depth / grad_alpha must be contiguous [H,W] float32 device tensors")
+    return ctypes.c_void_p(t.data_ptr())
 
 
 def device_params(params, device="cuda"):
@@ -107,6 +125,7 @@ class RasterContext:
         check(self._lib.gsplat_context_create(ctypes.byref(h), int(max_gaussians), int(max_width), int(max_height)))
         self._h = h
         self._last = None
+        self._depth = False
         self.max_gaussians, self.max_width, self.max_height = int(max_gaussians), int(max_width), int(max_height)
 
     def close(self):
@@ -144,6 +163,13 @@ class RasterContext:
         """Training through backward_pass: the forward stops storing Sigma, J, conic and the SH colour (the fused backward
         recomputes what it needs); those four views are then absent from the forward's result."""
         check(self._lib.gsplat_context_set_lean_forward(self._h, int(bool(enabled))))
+
+    def set_depth(self, enabled):
+        """Depth mode (gsplat_context_set_depth): every later forward also composites the per-pixel depth
+        sum alpha T z (the result's "depth" view), and backward_pass / backward_render / backward_pass_adam accept
+        grad_depth / grad_alpha."""
+        check(self._lib.gsplat_context_set_depth(self._h, int(bool(enabled))))
+        self._depth = bool(enabled)
 
     def set_preprocess_split(self, mode):
         """How the per-gaussian forward is launched: 0 (default) the single fused kernel, 1 SH colour then geometry on the
@@ -217,6 +243,11 @@ class RasterContext:
                  xyz_c=(fv.xyz_c_selected, (M, 3), "<f4"), sorted=(fv.sorted_gaussians, (S,), "<i4"),
                  ranges=(fv.splat_start_end_idx_by_tile_idx, (T + 1,), "<i4"), image=(fv.image, (H, W, 3), "<f4"),
                  T=(fv.weight_per_pixel, (H, W), "<f4"), n=(fv.splats_per_pixel, (H, W), "<i4")), self)
+        if self._depth:
+            dp = ctypes.c_void_p()
+            check(self._lib.gsplat_context_depth_map(self._h, ctypes.byref(dp)))
+            out._specs["depth"] = (dp.value, (H, W), "<f4")
+        out._derived["alpha"] = _alpha  # the opacity map: 1 - the final transmittance
         self._last = (g.num_gaussians, M, l_max)
         return out._all() if _EAGER_VIEWS else out
 
@@ -247,21 +278,30 @@ class RasterContext:
             setattr(gs, "grad_" + k, _ptr(grads.get(k)))
         return gs
 
-    def backward_pass(self, params, cam, grad_image, bg_color, l_max, grads):
-        """grads: dict from alloc_gradients (compacted order); every leaf gradient is overwritten."""
+    def backward_pass(self, params, cam, grad_image, bg_color, l_max, grads, grad_depth=None, grad_alpha=None):
+        """grads: dict from alloc_gradients (compacted order); every leaf gradient is overwritten.  grad_depth /
+        grad_alpha ([H,W], depth mode, either may be None): dL/d of the forward's "depth" / "alpha" views, added to the
+        image's gradient (gsplat_backward_pass_depth)."""
         g, c = self._structs(params, cam, l_max)
         gs = self._grad_struct(grads)
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(self._lib.gsplat_backward_pass(self._h, ctypes.byref(g), ctypes.byref(c), _ptr(grad_image),
-                                             float(bg_color), int(l_max), ctypes.byref(gs), st))
+        if grad_depth is None and grad_alpha is None:
+            check(self._lib.gsplat_backward_pass(self._h, ctypes.byref(g), ctypes.byref(c), _ptr(grad_image),
+                                                 float(bg_color), int(l_max), ctypes.byref(gs), st))
+        else:
+            check(self._lib.gsplat_backward_pass_depth(self._h, ctypes.byref(g), ctypes.byref(c), _ptr(grad_image),
+                                                       _map_ptr(grad_depth), _map_ptr(grad_alpha), float(bg_color),
+                                                       int(l_max), ctypes.byref(gs), st))
         return grads
 
-    def backward_pass_adam(self, params, cam, grad_image, bg_color, l_max, adam, grads=None):
+    def backward_pass_adam(self, params, cam, grad_image, bg_color, l_max, adam, grads=None, grad_depth=None,
+                           grad_alpha=None):
         """backward_pass with the optimizer step inside (single-GPU training): the compositing backward, then ONE
         per-gaussian kernel that differentiates every visible gaussian and applies the masked Adam step to its rows of the
         parameters (`params`, in place), the moments and the densification statistics (gsplat_backward_gaussians_adam).
-        adam: an _lib.AdamFused (AdamOptimizer.fused_state); grads: optional gradient arrays to fill as well."""
-        self.backward_render(grad_image, bg_color)
+        adam: an _lib.AdamFused (AdamOptimizer.fused_state); grads: optional gradient arrays to fill as well;
+        grad_depth / grad_alpha: as in backward_pass."""
+        self.backward_render(grad_image, bg_color, grad_depth=grad_depth, grad_alpha=grad_alpha)
         self.backward_gaussians_adam(params, cam, l_max, adam, grads)
 
     def backward_gaussians_adam(self, params, cam, l_max, adam, grads=None):
@@ -272,13 +312,21 @@ class RasterContext:
         check(self._lib.gsplat_backward_gaussians_adam(self._h, ctypes.byref(g), ctypes.byref(c), int(l_max),
                                                        ctypes.byref(adam), gs, st))
 
-    def backward_render(self, grad_image, bg_color, rgb_global=None, common=None, uv_norm=None):
+    def backward_render(self, grad_image, bg_color, rgb_global=None, common=None, uv_norm=None, grad_depth=None,
+                        grad_alpha=None):
         """First half of backward_pass: compositing backward; optionally this view's g_rgb in global order [N,3].
         common [N,12] (and uv_norm [N]): the split exchange's rows -- the rows of the gaussians this view culled are
-        cleared here, the others are written by backward_gaussians_split (gsplat_backward_render_split)."""
+        cleared here, the others are written by backward_gaussians_split (gsplat_backward_render_split).
+        grad_depth / grad_alpha: as in backward_pass; whichever per-gaussian call follows takes the depth term along
+        (gsplat_backward_render_depth)."""
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        check(self._lib.gsplat_backward_render_split(self._h, _ptr(grad_image), float(bg_color), _ptr(rgb_global),
-                                                     _ptr(common), _ptr(uv_norm), st))
+        if grad_depth is None and grad_alpha is None:
+            check(self._lib.gsplat_backward_render_split(self._h, _ptr(grad_image), float(bg_color), _ptr(rgb_global),
+                                                         _ptr(common), _ptr(uv_norm), st))
+        else:
+            check(self._lib.gsplat_backward_render_depth(self._h, _ptr(grad_image), _map_ptr(grad_depth),
+                                                         _map_ptr(grad_alpha), float(bg_color), _ptr(rgb_global),
+                                                         _ptr(common), _ptr(uv_norm), st))
 
     def backward_gaussians_split(self, params, cam, l_max, common, uv_norm=None, first=0, end=None):
         """Second half of backward_pass for a view-sharded step: the twelve direction-independent gradient columns go

@@ -52,7 +52,7 @@ extern "C" {
 const char *gsplat_last_error(void);
 /* Library ABI version (bumped when a signature changes); bindings compare it with the GSPLAT_ABI_VERSION they were
  * written against, so a stale prebuilt library fails at load time, not with a wrong argument list. */
-#define GSPLAT_ABI_VERSION 8
+#define GSPLAT_ABI_VERSION 9
 int gsplat_abi_version(void);
 /* What the loaded binary was built from: sha256 (first 16 hex digits) over the kernel sources (3dgs_amd/csrc: Makefile,
  * *.h, *.hip) at link time, and the extra compiler flags of a diagnostic build ("" for the product build).  A loader
@@ -467,6 +467,32 @@ int gsplat_backward_render_split(gsplat_context *ctx, const float *grad_image, f
 int gsplat_backward_gaussians_split(gsplat_context *ctx, const gsplat_gaussians *gaussians, const gsplat_camera *camera,
                                     int l_max, float *common, float *uv_norm, int first_gaussian, int end_gaussian,
                                     void *stream);
+
+/* ABI 9 -- differentiable depth and opacity maps.  With depth mode on, every forward of the context (training, lean and
+ * render-only alike) also composites the per-pixel depth in the same pass:
+ *   depth(p) = sum_{i < n(p)} alpha_i T_i z_i,   z_i = the camera-space depth of the gaussian (xyz_c.z),
+ * i.e. channel 0 of the image render_image would give for the colour (z, 1, 0) over background 0 (not divided by the
+ * opacity; the background adds nothing).  The opacity map needs nothing new: alpha(p) = 1 - weight_per_pixel(p).
+ *   gsplat_context_set_depth       forwards of this context render depth (0: they do not; the default);
+ *   gsplat_context_depth_map       the [H,W] depth of the last forward, valid until the next forward; an error when that
+ *                                  forward did not render depth;
+ *   gsplat_backward_render_depth   gsplat_backward_render_split with dL/d depth and dL/d alpha ([H,W] each, either may be
+ *                                  NULL = zero) next to dL/d image.  Every gradient becomes that of the total: the
+ *                                  compositing part (render_image_backward for colour (z, 1, 0), background 0) adds to
+ *                                  d/d opacity, conic and uv, and dL/dz = sum_p alpha T dL/d depth reaches grad_xyz (and
+ *                                  grad_xyz_c) through the per-gaussian call that follows -- whichever of
+ *                                  gsplat_backward_gaussians(_range, _split, _adam) it is.  Both NULL: exactly
+ *                                  gsplat_backward_render_split.  Depth or alpha gradients after a forward that did not
+ *                                  render depth: GSPLAT_ERR_INVALID_ARG before anything is launched;
+ *   gsplat_backward_pass_depth     gsplat_backward_pass with the two extra gradients. */
+int gsplat_context_set_depth(gsplat_context *ctx, int enabled);
+int gsplat_context_depth_map(gsplat_context *ctx, const float **depth);
+int gsplat_backward_render_depth(gsplat_context *ctx, const float *grad_image, const float *grad_depth,
+                                 const float *grad_alpha, float bg_color, float *rgb_global, float *common, float *uv_norm,
+                                 void *stream);
+int gsplat_backward_pass_depth(gsplat_context *ctx, const gsplat_gaussians *gaussians, const gsplat_camera *camera,
+                               const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
+                               int l_max, const gsplat_gradients *out, void *stream);
 
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
