@@ -380,10 +380,11 @@ def rasterize(params, camera, near_thresh, mh_dist, padding, bg, l_max, dtype=np
     return out
 
 
-def backward_pass(fwd, camera, grad_image, bg, l_max, dtype=np.float32, threads=1):
+def backward_pass(fwd, camera, grad_image, bg, l_max, dtype=np.float32, threads=1, tan_fov=None):
     """Restates TrainerImpl::backward_pass after fused_loss (cuda/trainer.cu:941-1012).
 
-    Returns gradients in compacted (post-cull) order, with the same '=' / '+=' chaining.
+    Returns gradients in compacted (post-cull) order, with the same '=' / '+=' chaining.  tan_fov: (x, y) to use in the
+    Jacobian's backward instead of numpy's tan(atan(.)) in float (which may round one ulp away from a host's tanf).
     """
     W, H = int(camera["width"]), int(camera["height"])
     g = {}
@@ -399,6 +400,8 @@ def backward_pass(fwd, camera, grad_image, bg, l_max, dtype=np.float32, threads=
     # cuda/trainer.cu:992-995: tan(atan(.)) in float
     tan_fovx = np.tan(rt(2.0) * np.arctan(rt(W) / (rt(2.0) * fx)) * rt(0.5))
     tan_fovy = np.tan(rt(2.0) * np.arctan(rt(H) / (rt(2.0) * fy)) * rt(0.5))
+    if tan_fov is not None:
+        tan_fovx, tan_fovy = rt(tan_fov[0]), rt(tan_fov[1])
     g["xyz_c"] = compute_projection_jacobian_backward(fwd["xyz_c"], fx, fy, tan_fovx, tan_fovy, g["J"], None, dtype)
     g["quaternion"], g["scale"] = compute_sigma_backward(fwd["quaternion"], fwd["scale"], g["sigma"], dtype)
     g["xyz_c"] = project_to_screen_backward(fwd["xyz_c"], camera["proj"], g["uv"], W, H, g["xyz_c"], dtype)

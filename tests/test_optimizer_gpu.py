@@ -153,7 +153,7 @@ def test_factored_sh_step_equals_the_stored_gradient_step(gpu, scene, name):
 
 
 @pytest.mark.parametrize("mode", [0, 1, 2])
-@pytest.mark.parametrize("name", ["small", "small_l1", "small_l0", "mid_l2"])
+@pytest.mark.parametrize("name", ["small", "small_l1", "small_l0", "mid_l2", "edge"])
 def test_backward_with_adam_inside_equals_backward_then_optimizer(gpu, scene, name, mode):
     """r06: gsplat_backward_gaussians_adam -- the per-gaussian backward that applies the masked Adam step itself -- must
     leave parameters, both moments of all six groups and the densification statistics BIT-identical to the backward that
@@ -162,11 +162,16 @@ def test_backward_with_adam_inside_equals_backward_then_optimizer(gpu, scene, na
     backward does.  Both twins differentiate the SAME compositing rows (one gsplat_backward_render: its float atomics
     reorder between launches).  Two steps: the second sees the moved parameters."""
     torch, raster, opt_mod = gpu, pkg("raster"), pkg("optimizer")
-    N, W, H, L = {"small": (5000, 256, 144, 3), "small_l1": (3000, 160, 96, 1), "small_l0": (3000, 160, 96, 0),
-                  "mid_l2": (40000, 320, 192, 2)}[name]
-    params = scene.make_gaussians(N, W, H, L)
-    params["xyz"][::3, 2] *= -1
-    cam = scene.make_camera(W, H, 1)
+    if name == "edge":  # clamped, near-plane, NaN-radius, needle, saturated rows (tests/edge_scenes.py), some culled
+        import edge_scenes
+        params, cam, _ = edge_scenes.make_edge_scene("small")
+        N, W, H, L = edge_scenes.SIZES["small"]
+    else:
+        N, W, H, L = {"small": (5000, 256, 144, 3), "small_l1": (3000, 160, 96, 1), "small_l0": (3000, 160, 96, 0),
+                      "mid_l2": (40000, 320, 192, 2)}[name]
+        params = scene.make_gaussians(N, W, H, L)
+        params["xyz"][::3, 2] *= -1
+        cam = scene.make_camera(W, H, 1)
     c = scene.CONFIG
     ctx = raster.RasterContext(N, W, H)
     dp_a, dc = raster.device_params(params), raster.device_camera(cam)
