@@ -210,6 +210,10 @@ SIGNATURES = {
     "gsplat_backward_render_depth": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _P]),
     "gsplat_backward_pass_depth": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _P, _P, _P, _F, _I,
                                         ctypes.POINTER(Gradients), _P]),
+    "gsplat_backward_gaussians_camera": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _I,
+                                              ctypes.POINTER(Gradients), _P, _P, _P]),
+    "gsplat_backward_pass_camera": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _P, _P, _P, _F, _I,
+                                         ctypes.POINTER(Gradients), _P, _P, _P]),
     "gsplat_context_set_preprocess_split": (_I, [_P, _I]),
     "gsplat_context_get_counters": (_I, [_P, ctypes.POINTER(ctypes.c_longlong), _I]),
     "gsplat_context_set_timing": (_I, [_P, _I]),

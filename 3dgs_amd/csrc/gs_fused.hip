@@ -132,6 +132,7 @@ struct gsplat_context {
   gs::DeviceBuffer chunk_first;  // [chunks of the index space]: slice-local rank of each chunk's first index (mode 2)
   gs::DeviceBuffer kept;     // slice-local lists of the kept gaussians (project_cull -> preprocess' compacted walk)
   gs::DeviceBuffer dir_grad;  // [M,3]: sh_adam_dir_kernel -> preprocess_bwd_kernel<L, 3> (gsplat_adam_fused.mode 2)
+  gs::DeviceBuffer cam_rows;  // [ceil(M/64),16] doubles: preprocess_bwd_kernel<.., kCamGrad> -> cam_grad_finalize_kernel
   gs::SortFork fork;         // side streams for the per-tile sorts of long lists (created when a forward first needs them)
   // the forward's record (gs_common.h: publish_record): pinned host memory the GPU writes and the host polls
   volatile unsigned long long *h_pub = nullptr;
@@ -182,7 +183,7 @@ struct gsplat_context {
     const gs::DeviceBuffer *all[] = {&mask, &counters, &rank, &xyz_c_all, &uv_all, &c2g, &xyz_c, &uv, &sigma, &conic, &J,
                                      &rgb, &radius, &recs, &counts, &offsets, &grad_rows, &hitmask, &keys_a, &keys_b, &pay_a, &pay_b,
                                      &sorted, &temp, &ranges, &image, &T_px, &n_px, &blockmasks, &kept, &tile_tops, &tile_order,
-                                     &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad,
+                                     &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad, &cam_rows,
                                      &depth_map, &seg_chk_d, &fseg_part_d};
     size_t b = 0;
     for (auto *p : all) b += p->bytes;
@@ -194,7 +195,7 @@ struct gsplat_context {
     gs::DeviceBuffer *all[] = {&mask, &counters, &rank, &xyz_c_all, &uv_all, &c2g, &xyz_c, &uv, &sigma, &conic, &J,
                                &rgb, &radius, &recs, &counts, &offsets, &grad_rows, &hitmask, &keys_a, &keys_b, &pay_a, &pay_b,
                                &sorted, &temp, &bin_table, &ranges, &image, &T_px, &n_px, &blockmasks, &kept, &tile_tops, &tile_order,
-                               &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad,
+                               &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad, &cam_rows,
                                &depth_map, &seg_chk_d, &fseg_part_d};
     for (auto *p : all) p->release();
     fseg_gran_zeroed = nullptr;
@@ -1031,7 +1032,10 @@ struct AdamFused {
 #endif
 // kDepthRow: the rows carry dL/dz of the composited depth in slot 9 (gsplat_backward_render_depth; gs_render.h:
 // DepthMaps) -- a template flag, so that the default instantiations stay exactly what they were
-template <int L, int kAdam = 0, bool kDepthRow = false>
+// kCamGrad (plain form only, whole range): every wave also sums its gaussians' shares of dL/d view[0..11] and
+// dL/d campos in double and one lane stores them as row (first slot / 64) of cam_rows [ceil(M/64), 16];
+// cam_grad_finalize_kernel sums the rows (gsplat_backward_gaussians_camera)
+template <int L, int kAdam = 0, bool kDepthRow = false, bool kCamGrad = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam == 3 ? GS_BWD3_WAVES : 3, 8))) void preprocess_bwd_kernel(gsplat_gaussians g, const float *__restrict__ view,
                                                                 const float *__restrict__ proj, int M,
                                                                 const int *__restrict__ c2g,
@@ -1040,7 +1044,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
                                                                 float tan_fovx, float tan_fovy, float fwd_tan_fovx,
                                                                 float fwd_tan_fovy, float mh_dist, float cx, float cy,
                                                                 float cz, int width, int height, BwdOut o,
-                                                                int ranged, int i_lo, int i_hi, AdamFused ad) {
+                                                                int ranged, int i_lo, int i_hi, AdamFused ad,
+                                                                double *__restrict__ cam_rows) {
+  static_assert(!kCamGrad || kAdam == 0, "the camera gradient is a form of the plain backward");
   // ranged: only the gaussians with global index in [i_lo, i_hi), i.e. the compacted slots [first slot whose global index
   // is >= i_lo, first slot whose global index is >= i_hi) (chunked backward of a view-sharded step: the exchange of one
   // chunk runs while the next is computed); the grid covers the largest possible chunk, blocks past its end leave at once.
@@ -1213,8 +1219,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
     __builtin_amdgcn_wave_barrier();
     if (o.sh) gs::rows_from_lds<kRest>(o.sh + (size_t)jw * kRest, wsh, rows, lane);
   }
-  if (!live) return;
+  if constexpr (!kCamGrad) {
+    if (!live) return;
+  }  // (kCamGrad: dead lanes go on with row jw's values, which they weigh 0 in the wave's sum, and store nothing)
   gx = 0.0f + gx; gy = 0.0f + gy; gz = 0.0f + gz;
+  [[maybe_unused]] const float g_dir[3] = {gx, gy, gz};  // the position gradient through the view direction alone
   // kAdam: one three-vector group of this lane's gaussian: parameter and moments at the GLOBAL row i
   auto step3 = [&](const float *pc, float *m, float *v, const float *gr, float lr) {
     float *p = const_cast<float *>(pc);
@@ -1240,7 +1249,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
   // conic -> (J, Sigma).  Sigma, J and the conic are RECOMPUTED from what this kernel reads anyway (quaternion, scale,
   // camera-space position) with the forward's functions and the forward's tan(fov): bit for bit the values
   // preprocess_kernel stored, without reading 60 bytes per gaussian back (the kernel is HBM bound).
-  const float x = xyz_c_sel[3 * j], y = xyz_c_sel[3 * j + 1], z = xyz_c_sel[3 * j + 2];
+  const int jc = kCamGrad ? jr : j;
+  const float x = xyz_c_sel[3 * jc], y = xyz_c_sel[3 * jc + 1], z = xyz_c_sel[3 * jc + 2];
   float Jv[6], sg[6], con[3], rad_unused[4], dJ[6], dS[6];
   {
     const float4 q = reinterpret_cast<const float4 *>(g.quaternion)[i];
@@ -1249,9 +1259,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
   }
   gs::jacobian(x, y, z, fx, fy, fwd_tan_fovx, fwd_tan_fovy, Jv);
   gs::conic_radius(Jv, sg, vw, mh_dist, con, rad_unused);
-  gs::conic_bwd(Jv, sg, vw, con, g_con, dJ, dS);
+  float dM[kCamGrad ? 6 : 1];
+  gs::conic_bwd<kCamGrad>(Jv, sg, vw, con, g_con, dJ, dS, dM);
 #pragma unroll
   for (int k = 0; k < 6; ++k) { dJ[k] = 0.0f + dJ[k]; dS[k] = 0.0f + dS[k]; }
+  [[maybe_unused]] float jt_dm[kCamGrad ? 9 : 1];  // dL/dW through M = J W: (J^T dM)[r][c]
+  if constexpr (kCamGrad) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) jt_dm[3 * r + k] = Jv[r] * dM[k] + Jv[3 + r] * dM[3 + k];
+  }
   // J -> xyz_c
   float cxg, cyg, czg;
   gs::jacobian_bwd(x, y, z, fx, fy, tan_fovx, tan_fovy, dJ, cxg, cyg, czg);
@@ -1293,39 +1311,113 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
     }
     if (!o.xyz) return;  // (gradient arrays: only when the caller asked for them)
   }
-  // stores
-  if constexpr (kAdam == 1) {
-    // what the optimizer kernels behind this one need: the position gradient and the colour gradient the SH gradients
-    // are made of; the other arrays only where the caller gave them
-    o.xyz[3 * j] = gx; o.xyz[3 * j + 1] = gy; o.xyz[3 * j + 2] = gz;
-    if (o.opacity) o.opacity[j] = g_op;
-    if (o.scale) { o.scale[3 * j] = dSc[0]; o.scale[3 * j + 1] = dSc[1]; o.scale[3 * j + 2] = dSc[2]; }
-    if (o.quaternion) reinterpret_cast<float4 *>(o.quaternion)[j] = make_float4(dQ[0], dQ[1], dQ[2], dQ[3]);
-  } else if (o.common) {  // the exchange's row, in global order (the same twelve values pack_split_kernel gathers)
-    gs::f4u *row = reinterpret_cast<gs::f4u *>(o.common + (size_t)i * 12);
-    row[0] = gs::f4u{gx, gy, gz, g_op};
-    row[1] = gs::f4u{dSc[0], dSc[1], dSc[2], dQ[0]};
-    row[2] = gs::f4u{dQ[1], dQ[2], dQ[3], 1.0f};
-    if (o.uv_norm) o.uv_norm[i] = sqrtf(g_u * g_u + g_v * g_v);  // pack_uv_norm_kernel's expression
-  } else {
-    o.xyz[3 * j] = gx; o.xyz[3 * j + 1] = gy; o.xyz[3 * j + 2] = gz;
-    o.opacity[j] = g_op;
-    o.scale[3 * j] = dSc[0]; o.scale[3 * j + 1] = dSc[1]; o.scale[3 * j + 2] = dSc[2];
-    reinterpret_cast<float4 *>(o.quaternion)[j] = make_float4(dQ[0], dQ[1], dQ[2], dQ[3]);
-  }
-  if (o.rgb) { o.rgb[3 * j] = b0g[0]; o.rgb[3 * j + 1] = b0g[1]; o.rgb[3 * j + 2] = b0g[2]; }
-  if (o.conic) { o.conic[3 * j] = g_con[0]; o.conic[3 * j + 1] = g_con[1]; o.conic[3 * j + 2] = g_con[2]; }
-  if (o.uv) { o.uv[2 * j] = g_u; o.uv[2 * j + 1] = g_v; }
-  if (o.pre_rgb) { o.pre_rgb[3 * j] = g_rgb[0]; o.pre_rgb[3 * j + 1] = g_rgb[1]; o.pre_rgb[3 * j + 2] = g_rgb[2]; }
-  if (o.J) {
+  // stores (kCamGrad: live lanes only, and only when the caller gave arrays -- `out` may be NULL there)
+  if (!kCamGrad || (live && o.xyz)) {
+    if constexpr (kAdam == 1) {
+      // what the optimizer kernels behind this one need: the position gradient and the colour gradient the SH gradients
+      // are made of; the other arrays only where the caller gave them
+      o.xyz[3 * j] = gx; o.xyz[3 * j + 1] = gy; o.xyz[3 * j + 2] = gz;
+      if (o.opacity) o.opacity[j] = g_op;
+      if (o.scale) { o.scale[3 * j] = dSc[0]; o.scale[3 * j + 1] = dSc[1]; o.scale[3 * j + 2] = dSc[2]; }
+      if (o.quaternion) reinterpret_cast<float4 *>(o.quaternion)[j] = make_float4(dQ[0], dQ[1], dQ[2], dQ[3]);
+    } else if (o.common) {  // the exchange's row, in global order (the same twelve values pack_split_kernel gathers)
+      gs::f4u *row = reinterpret_cast<gs::f4u *>(o.common + (size_t)i * 12);
+      row[0] = gs::f4u{gx, gy, gz, g_op};
+      row[1] = gs::f4u{dSc[0], dSc[1], dSc[2], dQ[0]};
+      row[2] = gs::f4u{dQ[1], dQ[2], dQ[3], 1.0f};
+      if (o.uv_norm) o.uv_norm[i] = sqrtf(g_u * g_u + g_v * g_v);  // pack_uv_norm_kernel's expression
+    } else {
+      o.xyz[3 * j] = gx; o.xyz[3 * j + 1] = gy; o.xyz[3 * j + 2] = gz;
+      o.opacity[j] = g_op;
+      o.scale[3 * j] = dSc[0]; o.scale[3 * j + 1] = dSc[1]; o.scale[3 * j + 2] = dSc[2];
+      reinterpret_cast<float4 *>(o.quaternion)[j] = make_float4(dQ[0], dQ[1], dQ[2], dQ[3]);
+    }
+    if (o.rgb) { o.rgb[3 * j] = b0g[0]; o.rgb[3 * j + 1] = b0g[1]; o.rgb[3 * j + 2] = b0g[2]; }
+    if (o.conic) { o.conic[3 * j] = g_con[0]; o.conic[3 * j + 1] = g_con[1]; o.conic[3 * j + 2] = g_con[2]; }
+    if (o.uv) { o.uv[2 * j] = g_u; o.uv[2 * j + 1] = g_v; }
+    if (o.pre_rgb) { o.pre_rgb[3 * j] = g_rgb[0]; o.pre_rgb[3 * j + 1] = g_rgb[1]; o.pre_rgb[3 * j + 2] = g_rgb[2]; }
+    if (o.J) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) o.J[6 * j + k] = dJ[k];
-  }
-  if (o.sigma) {
+      for (int k = 0; k < 6; ++k) o.J[6 * j + k] = dJ[k];
+    }
+    if (o.sigma) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) o.sigma[6 * j + k] = dS[k];
+      for (int k = 0; k < 6; ++k) o.sigma[6 * j + k] = dS[k];
+    }
+    if (o.xyz_c) { o.xyz_c[3 * j] = cxg; o.xyz_c[3 * j + 1] = cyg; o.xyz_c[3 * j + 2] = czg; }
   }
-  if (o.xyz_c) { o.xyz_c[3 * j] = cxg; o.xyz_c[3 * j + 1] = cyg; o.xyz_c[3 * j + 2] = czg; }
+  if constexpr (kCamGrad) {
+    // This lane's share, in double: view[4r + c] += c_r p_c + (J^T dM)[r][c], view[4r + 3] += c_r, campos -= s, with
+    // c = dL/d xyz_c (cxg..: Jacobian, screen and depth terms), p the world position, s the view-direction term.  Dead
+    // lanes add exact zeros (a select, not a product: their row-jw values may be anything).  Then a fixed xor
+    // butterfly over the wave that halves what a lane carries at every step (lane bit 5 keeps sums 0-7 or 8-15, bit 4
+    // four of those, ...): 8 + 4 + 2 + 1 + 1 + 1 exchanges instead of 15 per step, and sum k = lane >> 2 ends in the
+    // quad of lanes 4k..4k+3 -- the same bits in every run.
+    const double p[3] = {g.xyz[3 * i], g.xyz[3 * i + 1], g.xyz[3 * i + 2]};
+    const double cv[3] = {cxg, cyg, czg};
+    double v[16];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) v[4 * r + k] = live ? cv[r] * p[k] + (double)jt_dm[3 * r + k] : 0.0;
+      v[4 * r + 3] = live ? cv[r] : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[12 + k] = live ? -(double)g_dir[k] : 0.0;
+    v[15] = 0.0;
+#pragma unroll
+    for (int half = 8, bit = 32; half >= 1; half >>= 1, bit >>= 1) {
+      const bool upper = (lane & bit) != 0;
+#pragma unroll
+      for (int k = 0; k < half; ++k) {
+        const double send = upper ? v[k] : v[k + half], keep = upper ? v[k + half] : v[k];
+        v[k] = keep + __shfl_xor(send, bit, 64);
+      }
+    }
+    v[0] += __shfl_xor(v[0], 2, 64);
+    v[0] += __shfl_xor(v[0], 1, 64);
+    if ((lane & 3) == 0) cam_rows[(size_t)(jw >> 6) * 16 + (lane >> 2)] = v[0];  // (sum 15 is the zero pad)
+  }
+}
+
+// kCamGrad's second half: one workgroup sums the waves' rows in a fixed order -- thread t the component pair t & 7 of
+// rows t >> 3, (t >> 3) + 128, ..., then a tree over the 128 partial rows in LDS -- in double, and overwrites the fifteen
+// float results.  No atomics and no hand-off between workgroups: the same bits in every run.
+constexpr int kCamFinThreads = 1024;
+__global__ __launch_bounds__(kCamFinThreads) void cam_grad_finalize_kernel(const double *__restrict__ rows, int n_rows,
+                                                                           float *__restrict__ grad_view,
+                                                                           float *__restrict__ grad_campos) {
+  constexpr int kSlots = kCamFinThreads / 8;
+  __shared__ double2 s_part[kCamFinThreads];
+  const int t = threadIdx.x, piece = t & 7;
+  const double2 *r2 = reinterpret_cast<const double2 *>(rows);
+  double2 acc = make_double2(0.0, 0.0);
+#pragma unroll 8
+  for (int r = t >> 3; r < n_rows; r += kSlots) {
+    const double2 v = r2[(size_t)r * 8 + piece];
+    acc.x += v.x;
+    acc.y += v.y;
+  }
+  s_part[t] = acc;
+  __syncthreads();
+  for (int half = kCamFinThreads / 2; half >= 8; half >>= 1) {  // (half is a multiple of 8: partners share a piece)
+    if (t < half) {
+      const double2 o = s_part[t + half];
+      s_part[t].x += o.x;
+      s_part[t].y += o.y;
+    }
+    __syncthreads();
+  }
+  if (t < 8) {
+    const double2 v = s_part[t];
+    const double pair[2] = {v.x, v.y};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = 2 * t + h;
+      if (k < 12) grad_view[k] = (float)pair[h];
+      else if (k < 15) grad_campos[k - 12] = (float)pair[h];
+    }
+  }
 }
 
 // r06 (gsplat_adam_fused.mode 2): the SH group's Adam step and gs::sh_bwd's sums over the coefficient rows in ONE read of
@@ -2399,7 +2491,8 @@ int gsplat_backward_gaussians(gsplat_context *c, const gsplat_gaussians *g, cons
 
 static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
                                    const gsplat_gradients *out, float *common, float *uv_norm, int first_gaussian,
-                                   int end_gaussian, void *stream, const AdamFused *adam = nullptr, int adam_mode = 2);
+                                   int end_gaussian, void *stream, const AdamFused *adam = nullptr, int adam_mode = 2,
+                                   float *grad_view = nullptr, float *grad_campos = nullptr);
 
 int gsplat_backward_gaussians_range(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
                                     const gsplat_gradients *out, int first_gaussian, int end_gaussian, void *stream) {
@@ -2469,15 +2562,22 @@ int gsplat_backward_gaussians_adam(gsplat_context *c, const gsplat_gaussians *g,
 
 static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
                                    const gsplat_gradients *out, float *common, float *uv_norm, int first_gaussian,
-                                   int end_gaussian, void *stream, const AdamFused *adam, int adam_mode) {
+                                   int end_gaussian, void *stream, const AdamFused *adam, int adam_mode,
+                                   float *grad_view, float *grad_campos) {
   GS_REQUIRE(c && g && cam, "null argument struct");
   GS_REQUIRE(0 <= first_gaussian && first_gaussian <= end_gaussian && end_gaussian <= g->num_gaussians, "bad gaussian range");
   GS_REQUIRE(c->have_forward && c->rows_ready, "gsplat_backward_render has not run for this forward pass");
   GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
              "backward arguments do not match the recorded forward pass");
+  const bool cam_grad = grad_view != nullptr;  // gsplat_backward_gaussians_camera: whole range, plain form
+  if (cam_grad) {
+    GS_REQUIRE_DEV(grad_view); GS_REQUIRE_DEV(grad_campos);
+    GS_REQUIRE(!adam && !common && first_gaussian == 0 && end_gaussian == g->num_gaussians, "internal: camera form");
+  }
   static const gsplat_gradients kNoArrays = {};
   if (!out) out = &kNoArrays;  // split form: the twelve common columns go to `common`, nothing else is stored
-  if (!common && !(adam && (out == &kNoArrays || adam_mode == 1))) {  // (the Adam forms store only the arrays they are given)
+  // (the Adam forms store only the arrays they are given; the camera form may be given none)
+  if (!common && !(adam && (out == &kNoArrays || adam_mode == 1)) && !(cam_grad && out == &kNoArrays)) {
     GS_REQUIRE_DEV(out->grad_xyz); GS_REQUIRE_DEV(out->grad_rgb); GS_REQUIRE_DEV(out->grad_opacity);
     GS_REQUIRE_DEV(out->grad_scale); GS_REQUIRE_DEV(out->grad_quaternion);
     GS_REQUIRE(((uintptr_t)out->grad_quaternion & 15) == 0, "grad_quaternion must be 16-byte aligned");
@@ -2498,38 +2598,39 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
   // range's compacted slots in compact_to_global on the device (first_slot_not_below)
   const bool whole = first_gaussian == 0 && end_gaussian == g->num_gaussians;
   const int span = whole ? M : std::min(M, end_gaussian - first_gaussian);
-  if (span == 0) return GSPLAT_OK;
+  const int n_cam_rows = gs::div_up(span, 64);  // kCamGrad: one row of partial sums per wave
+  if (cam_grad && span > 0) {
+    const int rc = c->cam_rows.reserve((size_t)n_cam_rows * 16 * sizeof(double), st);
+    if (rc) return rc;
+  }
+  if (span == 0) {
+    if (cam_grad) {  // nothing visible: the camera gradient is zero, not what the buffers held
+      GS_HIP(hipMemsetAsync(grad_view, 0, 12 * sizeof(float), st));
+      GS_HIP(hipMemsetAsync(grad_campos, 0, 3 * sizeof(float), st));
+    }
+    return GSPLAT_OK;
+  }
   const int ranged = whole ? 0 : 1;
   const dim3 grid(gs::div_up(span, kBlock)), block(kBlock);
   c->mark(7, false, st);
   static const AdamFused kNoAdam = {};  // (value-initialised: every pointer null)
 #define GS_BWD(LL) do { if (c->rows_depth) GS_BWD2(LL, true); else GS_BWD2(LL, false); } while (0)
+#define GS_BWD_ARGS(AD, ROWS)                                                                                          \
+  (*g, cam->view, cam->proj, M, c->c2g.as<int>(), c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx,   \
+   tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist, cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo, ranged, \
+   first_gaussian, end_gaussian, AD, ROWS)
 #define GS_BWD2(LL, DR)                                                                                                \
   do {                                                                                                                 \
     if (adam && adam_mode == 1)                                                                                        \
-      preprocess_bwd_kernel<LL, 1, DR><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),              \
-                                                    c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx, \
-                                                    tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist,                  \
-                                                    cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo,          \
-                                                    ranged, first_gaussian, end_gaussian, *adam);                      \
+      preprocess_bwd_kernel<LL, 1, DR><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                            \
     else if (adam && adam_mode == 3)                                                                                   \
-      preprocess_bwd_kernel<LL, 3, DR><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),              \
-                                                    c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx, \
-                                                    tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist,                  \
-                                                    cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo,          \
-                                                    ranged, first_gaussian, end_gaussian, *adam);                      \
+      preprocess_bwd_kernel<LL, 3, DR><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                            \
     else if (adam)                                                                                                     \
-      preprocess_bwd_kernel<LL, 2, DR><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),           \
-                                                    c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx, \
-                                                    tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist,                  \
-                                                    cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo,          \
-                                                    ranged, first_gaussian, end_gaussian, *adam);                      \
+      preprocess_bwd_kernel<LL, 2, DR><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                            \
+    else if (cam_grad)                                                                                                 \
+      preprocess_bwd_kernel<LL, 0, DR, true><<<grid, block, 0, st>>> GS_BWD_ARGS(kNoAdam, c->cam_rows.as<double>());   \
     else                                                                                                               \
-      preprocess_bwd_kernel<LL, 0, DR><<<grid, block, 0, st>>>(*g, cam->view, cam->proj, M, c->c2g.as<int>(),          \
-                                                    c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx, \
-                                                    tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist,                  \
-                                                    cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo,          \
-                                                    ranged, first_gaussian, end_gaussian, kNoAdam);                    \
+      preprocess_bwd_kernel<LL, 0, DR><<<grid, block, 0, st>>> GS_BWD_ARGS(kNoAdam, nullptr);                          \
   } while (0)
   switch (l_max) {
     case 0: GS_BWD(0); break;
@@ -2539,7 +2640,12 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
   }
 #undef GS_BWD
 #undef GS_BWD2
+#undef GS_BWD_ARGS
   GS_LAUNCH_CHECK();
+  if (cam_grad) {
+    cam_grad_finalize_kernel<<<1, kCamFinThreads, 0, st>>>(c->cam_rows.as<double>(), n_cam_rows, grad_view, grad_campos);
+    GS_LAUNCH_CHECK();
+  }
   c->mark(7, true, st);
   return GSPLAT_OK;
 }
@@ -2573,6 +2679,39 @@ int gsplat_backward_pass_depth(gsplat_context *c, const gsplat_gaussians *g, con
   int rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, nullptr, nullptr, nullptr, stream);
   if (rc) return rc;
   return gsplat_backward_gaussians(c, g, cam, l_max, out, stream);
+}
+
+int gsplat_backward_gaussians_camera(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
+                                     const gsplat_gradients *out, float *grad_view, float *grad_campos, void *stream) {
+  GS_REQUIRE_DEV(grad_view); GS_REQUIRE_DEV(grad_campos);
+  return backward_gaussians_impl(c, g, cam, l_max, out, nullptr, nullptr, 0, g ? g->num_gaussians : 0, stream, nullptr, 2,
+                                 grad_view, grad_campos);
+}
+
+int gsplat_backward_pass_camera(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                                const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
+                                int l_max, const gsplat_gradients *out, float *grad_view, float *grad_campos,
+                                void *stream) {
+  // every check of the two calls below before the first launch
+  GS_REQUIRE(c && g && cam, "null argument struct");
+  GS_REQUIRE(c->have_forward, "no forward pass recorded in this context");
+  GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
+             "backward arguments do not match the recorded forward pass");
+  GS_REQUIRE_DEV(grad_view); GS_REQUIRE_DEV(grad_campos);
+  if (out) {
+    GS_REQUIRE_DEV(out->grad_xyz); GS_REQUIRE_DEV(out->grad_rgb); GS_REQUIRE_DEV(out->grad_opacity);
+    GS_REQUIRE_DEV(out->grad_scale); GS_REQUIRE_DEV(out->grad_quaternion);
+    GS_REQUIRE(((uintptr_t)out->grad_quaternion & 15) == 0, "grad_quaternion must be 16-byte aligned");
+    if (l_max > 0 && out->grad_sh) GS_REQUIRE_DEV(out->grad_sh);
+  }
+  GS_REQUIRE_DEV(grad_image);
+  if (grad_depth) GS_REQUIRE_DEV(grad_depth);
+  if (grad_alpha) GS_REQUIRE_DEV(grad_alpha);
+  GS_REQUIRE(!(grad_depth || grad_alpha) || c->depth_ready,
+             "depth / alpha gradients need a forward that rendered depth (gsplat_context_set_depth)");
+  int rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, nullptr, nullptr, nullptr, stream);
+  if (rc) return rc;
+  return gsplat_backward_gaussians_camera(c, g, cam, l_max, out, grad_view, grad_campos, stream);
 }
 
 int gsplat_context_set_depth(gsplat_context *c, int enabled) {

@@ -431,8 +431,10 @@ __device__ __forceinline__ void jacobian_bwd(float x, float y, float z, float fx
 }
 
 // ---- H2 (reference: conic_backward_kernel, cuda/gaussian_backward.cu:97-248): increments for J_grad[6], sigma_grad[6]
+// kDM: also hands back dL/dM (M = J W, 2x3 row-major) in dM[6] -- what the camera gradient needs (dL/dW = J^T dL/dM)
+template <bool kDM = false>
 __device__ __forceinline__ void conic_bwd(const float *J, const float *s, const Mat34 &vw, const float *c,
-                                          const float *dc, float *dJ /*6*/, float *dS /*6*/) {
+                                          const float *dc, float *dJ /*6*/, float *dS /*6*/, float *dM = nullptr) {
   const MV a = mv_from(J, s, vw);
   const float *m = a.m, *v = a.v;
   const float t00 = c[0] * dc[0] + c[1] * dc[1], t01 = c[0] * dc[1] + c[1] * dc[2];
@@ -457,6 +459,7 @@ __device__ __forceinline__ void conic_bwd(const float *J, const float *s, const 
               dmv12 = dv01 * s[2] + dv11 * s[4] + dv21 * s[5];
   const float dm00 = dmc00 + dmv00, dm01 = dmc01 + dmv01, dm02 = dmc02 + dmv02;
   const float dm10 = dmc10 + dmv10, dm11 = dmc11 + dmv11, dm12 = dmc12 + dmv12;
+  if constexpr (kDM) { dM[0] = dm00; dM[1] = dm01; dM[2] = dm02; dM[3] = dm10; dM[4] = dm11; dM[5] = dm12; }
   const float w00 = vw.m[0], w01 = vw.m[1], w02 = vw.m[2], w10 = vw.m[4], w11 = vw.m[5], w12 = vw.m[6],
               w20 = vw.m[8], w21 = vw.m[9], w22 = vw.m[10];
   dJ[0] = dm00 * w00 + dm01 * w01 + dm02 * w02;

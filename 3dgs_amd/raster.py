@@ -345,6 +345,35 @@ class RasterContext:
         check(self._lib.gsplat_backward_gaussians(self._h, ctypes.byref(g), ctypes.byref(c), int(l_max), ctypes.byref(gs), st))
         return grads
 
+    def backward_pass_camera(self, params, cam, grad_image, bg_color, l_max, grads=None, grad_depth=None, grad_alpha=None):
+        """backward_pass that also returns dL/d view[0..11] as grad_view [3,4] and dL/d campos as grad_campos [3] (device
+        float32 tensors; view and campos taken as two independent inputs -- 3dgs_amd/pose.py turns them into the pose's
+        gradient).  grads=None: only the camera gradient (pose refinement, localisation against frozen gaussians);
+        otherwise filled bit-identically to backward_pass.  Returns (grads, grad_view, grad_campos)
+        (gsplat_backward_pass_camera)."""
+        g, c = self._structs(params, cam, l_max)
+        gv, gc = self._camera_grads()
+        gs = ctypes.byref(self._grad_struct(grads)) if grads is not None else None
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self._lib.gsplat_backward_pass_camera(self._h, ctypes.byref(g), ctypes.byref(c), _ptr(grad_image),
+                                                    _map_ptr(grad_depth), _map_ptr(grad_alpha), float(bg_color),
+                                                    int(l_max), gs, _ptr(gv), _ptr(gc), st))
+        return grads, gv, gc
+
+    def backward_gaussians_camera(self, params, cam, l_max, grads=None):
+        """backward_pass_camera's second half, after backward_render (gsplat_backward_gaussians_camera)."""
+        g, c = self._structs(params, cam, l_max)
+        gv, gc = self._camera_grads()
+        gs = ctypes.byref(self._grad_struct(grads)) if grads is not None else None
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self._lib.gsplat_backward_gaussians_camera(self._h, ctypes.byref(g), ctypes.byref(c), int(l_max), gs,
+                                                         _ptr(gv), _ptr(gc), st))
+        return grads, gv, gc
+
+    @staticmethod
+    def _camera_grads():
+        return (torch.empty(3, 4, dtype=torch.float32, device="cuda"), torch.empty(3, dtype=torch.float32, device="cuda"))
+
     def backward_gaussians_range(self, params, cam, l_max, grads, first, end):
         """The per-gaussian chain for the gaussians with global index in [first, end) (chunked exchange)."""
         g, c = self._structs(params, cam, l_max)

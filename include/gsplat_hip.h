@@ -494,6 +494,30 @@ int gsplat_backward_pass_depth(gsplat_context *ctx, const gsplat_gaussians *gaus
                                const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
                                int l_max, const gsplat_gradients *out, void *stream);
 
+/* Camera gradient (no ABI bump: new entry points only).  view (camera->view[0..11] = [R|t]) and campos are two
+ * independent inputs, as the forward reads them.  With c_j = dL/d xyz_c of visible gaussian j (projection, screen and
+ * depth terms), p_j its world position, dM_j = dL/dM for M = J R and s_j its position gradient through the SH view
+ * direction:
+ *   grad_view[4r + c] = sum_j c_j[r] p_j[c] + sum_j (J_j^T dM_j)[r][c],  grad_view[4r + 3] = sum_j c_j[r]   (r, c < 3)
+ *   grad_campos       = -sum_j s_j
+ * summed in double in a fixed order (the same bits in every run) and written as float (device arrays of 12 and 3,
+ * overwritten; zeros when nothing is visible).  The intrinsics get no gradient.  A camera whose campos is -R^T t has
+ * one pose: 3dgs_amd/pose.py turns the fifteen numbers into its gradient.  The _range, _split and _adam backwards
+ * produce no camera gradient.
+ *   gsplat_backward_gaussians_camera  gsplat_backward_gaussians that also writes grad_view / grad_campos; its gradient
+ *                                     arrays are bit-identical to gsplat_backward_gaussians'.  out may be NULL: then only
+ *                                     the camera gradient is produced (pose refinement, localisation).  Needs
+ *                                     gsplat_backward_render or gsplat_backward_render_depth since the last forward;
+ *   gsplat_backward_pass_camera       gsplat_backward_pass / gsplat_backward_pass_depth (grad_depth, grad_alpha may both
+ *                                     be NULL) + the camera gradient. */
+int gsplat_backward_gaussians_camera(gsplat_context *ctx, const gsplat_gaussians *gaussians, const gsplat_camera *camera,
+                                     int l_max, const gsplat_gradients *out, float *grad_view, float *grad_campos,
+                                     void *stream);
+int gsplat_backward_pass_camera(gsplat_context *ctx, const gsplat_gaussians *gaussians, const gsplat_camera *camera,
+                                const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
+                                int l_max, const gsplat_gradients *out, float *grad_view, float *grad_campos,
+                                void *stream);
+
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
  * tiles, stable radix sorts on (depth bits, tile).  1 / 2 force one route.  Both produce identical lists. */
