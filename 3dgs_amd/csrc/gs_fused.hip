@@ -58,7 +58,7 @@ int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorte
                       float *g_rgb, float *g_opacity, float *g_uv, float *g_conic, hipStream_t st,
                       const unsigned short *masks_in, hipEvent_t ev_start, hipEvent_t ev_stop, const int *order,
                       const TileSegments *segments,
-                      const DepthMaps *depth);
+                      const DepthMaps *depth, bool absgrad);
 int launch_tile_segments(const int *ranges, const int *tops, int num_tiles, const TileSegments &seg, hipStream_t st);
 int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
 bool tile_order_supported(int num_tiles);
@@ -103,6 +103,10 @@ struct gsplat_context {
   bool depth_ready = false;  // the recorded forward rendered depth_map
   bool rows_depth = false;   // the gradient rows carry dL/dz in slot 9 (gsplat_backward_render_depth with depth gradients)
   gs::DeviceBuffer depth_map, seg_chk_d, fseg_part_d;
+  // absgrad mode (gsplat_context_set_absgrad): the compositing backward also sums every pixel's share of dL/d uv by absolute
+  // value, into row slots 10 and 11 (gs_render.h: row_moments9r_abs); the densification statistics are made of those
+  bool absgrad = false;
+  bool rows_abs = false;  // the gradient rows carry those sums (the last compositing backward ran in absgrad mode)
   void *fseg_gran_zeroed = nullptr;  // the granule block whose tags have been cleared (a fresh block holds anything)
   size_t fseg_gran_zeroed_bytes = 0;
   unsigned int fseg_epoch = 0;
@@ -1035,7 +1039,11 @@ struct AdamFused {
 // kCamGrad (plain form only, whole range): every wave also sums its gaussians' shares of dL/d view[0..11] and
 // dL/d campos in double and one lane stores them as row (first slot / 64) of cam_rows [ceil(M/64), 16];
 // cam_grad_finalize_kernel sums the rows (gsplat_backward_gaussians_camera)
-template <int L, int kAdam = 0, bool kDepthRow = false, bool kCamGrad = false>
+// kAbsRow: the rows carry the absolute sums of the pixels' shares of dL/d uv in slots 10 and 11 (absgrad mode,
+// gsplat_context_set_absgrad), and the densification statistic -- uv_norm of the split form, uv_grad_accum of the Adam
+// forms -- is their norm instead of |grad_uv|; every gradient is what it is without the flag.  (The camera form stores no
+// statistic and has no such instantiation.)
+template <int L, int kAdam = 0, bool kDepthRow = false, bool kCamGrad = false, bool kAbsRow = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam == 3 ? GS_BWD3_WAVES : 3, 8))) void preprocess_bwd_kernel(gsplat_gaussians g, const float *__restrict__ view,
                                                                 const float *__restrict__ proj, int M,
                                                                 const int *__restrict__ c2g,
@@ -1047,6 +1055,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
                                                                 int ranged, int i_lo, int i_hi, AdamFused ad,
                                                                 double *__restrict__ cam_rows) {
   static_assert(!kCamGrad || kAdam == 0, "the camera gradient is a form of the plain backward");
+  static_assert(!(kCamGrad && kAbsRow), "the camera form stores no densification statistic");
   // ranged: only the gaussians with global index in [i_lo, i_hi), i.e. the compacted slots [first slot whose global index
   // is >= i_lo, first slot whose global index is >= i_hi) (chunked backward of a view-sharded step: the exchange of one
   // chunk runs while the next is computed); the grid covers the largest possible chunk, blocks past its end leave at once.
@@ -1204,6 +1213,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
   const float g_op = a.w;
   const float g_con[3] = {b.x, b.y, b.z};
   const float g_u = b.w, g_v = c.x;
+  // the densification statistic's two components: the gradient's, or (kAbsRow) the absolute sums of slots 10 and 11
+  const float n_u = kAbsRow ? c.z : g_u, n_v = kAbsRow ? c.w : g_v;
   if constexpr (kAdam == 3 && kRest > 0) {
     // gs::sh_bwd's two results from elsewhere: band 0's gradient is its own expression (Y_0 is the constant), the position
     // gradient through the view direction is what sh_adam_dir_kernel left (the same sums in the same order)
@@ -1243,7 +1254,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
       gs::adam_values(pv, mv, vv, g_op, ad.lr_op, ad.b1, ad.b2, ad.eps, ad.bias1, ad.bias2);
       const_cast<float *>(g.opacity)[i] = pv; ad.m_op[i] = mv; ad.v_op[i] = vv;
     }
-    if (ad.uv_accum) ad.uv_accum[i] += sqrtf(g_u * g_u + g_v * g_v);
+    if (ad.uv_accum) ad.uv_accum[i] += sqrtf(n_u * n_u + n_v * n_v);
     if (ad.accum_dur) ad.accum_dur[i] += 1;
   }
   // conic -> (J, Sigma).  Sigma, J and the conic are RECOMPUTED from what this kernel reads anyway (quaternion, scale,
@@ -1325,7 +1336,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
       row[0] = gs::f4u{gx, gy, gz, g_op};
       row[1] = gs::f4u{dSc[0], dSc[1], dSc[2], dQ[0]};
       row[2] = gs::f4u{dQ[1], dQ[2], dQ[3], 1.0f};
-      if (o.uv_norm) o.uv_norm[i] = sqrtf(g_u * g_u + g_v * g_v);  // pack_uv_norm_kernel's expression
+      if (o.uv_norm) o.uv_norm[i] = sqrtf(n_u * n_u + n_v * n_v);  // pack_uv_norm_kernel's expression
     } else {
       o.xyz[3 * j] = gx; o.xyz[3 * j + 1] = gy; o.xyz[3 * j + 2] = gz;
       o.opacity[j] = g_op;
@@ -1618,6 +1629,29 @@ __global__ __launch_bounds__(kBlock) void pack_uv_norm_kernel(const unsigned cha
     val = sqrtf(g.x * g.x + g.y * g.y);
   }
   out[i] = val;
+}
+
+// absgrad mode: the norm of row slots 10 and 11 (the absolute sums of the pixels' shares of dL/d uv) in global gaussian
+// order, 0 where culled -- pack_uv_norm_kernel's counterpart, in preprocess_bwd_kernel<.., kAbsRow>'s expression
+__global__ __launch_bounds__(kBlock) void pack_abs_norm_kernel(const unsigned char *__restrict__ mask,
+                                                               const int *__restrict__ rank_of, int N,
+                                                               const float4 *__restrict__ rows, float *__restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  float val = 0.0f;
+  if (mask[i]) {
+    const float4 c = rows[4 * (size_t)rank_of[i] + 2];
+    val = sqrtf(c.z * c.z + c.w * c.w);
+  }
+  out[i] = val;
+}
+
+// ... and the two sums themselves, compacted order
+__global__ __launch_bounds__(kBlock) void copy_abs_uv_kernel(const float4 *__restrict__ rows, int M, float2 *__restrict__ out) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= M) return;
+  const float4 c = rows[4 * (size_t)j + 2];
+  out[j] = make_float2(c.z, c.w);
 }
 
 // Split exchange: the 12 direction-independent columns (SUM all-reduce) and this view's g_rgb (all-gather).
@@ -1950,6 +1984,7 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
   c->order_ready = false;
   c->depth_ready = false;
   c->rows_depth = false;
+  c->rows_abs = false;
   gs::pool_unwatch(&c->last_mask);
   c->last_mask = nullptr;  // rank[] and compact_to_global are about to be overwritten
   {  // outputs the caller took over (gsplat_context_detach_forward_outputs) come back from the pool, at their old sizes
@@ -2446,6 +2481,7 @@ int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, con
   const int M = c->M, W = c->width, H = c->height;
   c->rows_ready = false;
   c->rows_depth = false;
+  c->rows_abs = false;
   c->backward_seen = true;
   if (!c->rows_zeroed) {  // first backward of the context, or a second backward of the same forward
     c->mark(5, false, st);
@@ -2469,7 +2505,7 @@ int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, con
                                  c->blockmasks.as<unsigned short>(), timed ? c->ev[c->slot][12] : nullptr,
                                  timed ? c->ev[c->slot][13] : nullptr,
                                  (c->order_ready && !gs_no_tile_order()) ? c->tile_order.as<int>() : nullptr,
-                                 c->seg_ready ? &seg : nullptr, depth ? &dm : nullptr);
+                                 c->seg_ready ? &seg : nullptr, depth ? &dm : nullptr, c->absgrad);
   if (rc) return rc;
   if (c->seg_ready) c->n_segmented_backwards++;
   if (c->order_ready && !gs_no_tile_order()) c->n_ordered_backwards++;
@@ -2481,6 +2517,7 @@ int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, con
   }
   c->rows_ready = true;
   c->rows_depth = depth;
+  c->rows_abs = c->absgrad;
   return GSPLAT_OK;
 }
 
@@ -2614,23 +2651,24 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
   const dim3 grid(gs::div_up(span, kBlock)), block(kBlock);
   c->mark(7, false, st);
   static const AdamFused kNoAdam = {};  // (value-initialised: every pointer null)
-#define GS_BWD(LL) do { if (c->rows_depth) GS_BWD2(LL, true); else GS_BWD2(LL, false); } while (0)
+#define GS_BWD(LL) do { if (c->rows_depth) GS_BWD1(LL, true); else GS_BWD1(LL, false); } while (0)
+#define GS_BWD1(LL, DR) do { if (c->rows_abs) GS_BWD2(LL, DR, true); else GS_BWD2(LL, DR, false); } while (0)
 #define GS_BWD_ARGS(AD, ROWS)                                                                                          \
   (*g, cam->view, cam->proj, M, c->c2g.as<int>(), c->xyz_c.as<float>(), c->grad_rows.as<float4>(), fx, fy, tan_fovx,   \
    tan_fovy, fwd_tan_fovx, fwd_tan_fovy, c->mh_dist, cam->campos[0], cam->campos[1], cam->campos[2], W, H, bo, ranged, \
    first_gaussian, end_gaussian, AD, ROWS)
-#define GS_BWD2(LL, DR)                                                                                                \
+#define GS_BWD2(LL, DR, AB)                                                                                            \
   do {                                                                                                                 \
     if (adam && adam_mode == 1)                                                                                        \
-      preprocess_bwd_kernel<LL, 1, DR><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                            \
+      preprocess_bwd_kernel<LL, 1, DR, false, AB><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                 \
     else if (adam && adam_mode == 3)                                                                                   \
-      preprocess_bwd_kernel<LL, 3, DR><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                            \
+      preprocess_bwd_kernel<LL, 3, DR, false, AB><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                 \
     else if (adam)                                                                                                     \
-      preprocess_bwd_kernel<LL, 2, DR><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                            \
-    else if (cam_grad)                                                                                                 \
+      preprocess_bwd_kernel<LL, 2, DR, false, AB><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                 \
+    else if (cam_grad) /* (stores no statistic: one form for both) */                                                  \
       preprocess_bwd_kernel<LL, 0, DR, true><<<grid, block, 0, st>>> GS_BWD_ARGS(kNoAdam, c->cam_rows.as<double>());   \
     else                                                                                                               \
-      preprocess_bwd_kernel<LL, 0, DR><<<grid, block, 0, st>>> GS_BWD_ARGS(kNoAdam, nullptr);                          \
+      preprocess_bwd_kernel<LL, 0, DR, false, AB><<<grid, block, 0, st>>> GS_BWD_ARGS(kNoAdam, nullptr);               \
   } while (0)
   switch (l_max) {
     case 0: GS_BWD(0); break;
@@ -2639,6 +2677,7 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
     default: GS_BWD(3); break;
   }
 #undef GS_BWD
+#undef GS_BWD1
 #undef GS_BWD2
 #undef GS_BWD_ARGS
   GS_LAUNCH_CHECK();
@@ -2717,6 +2756,39 @@ int gsplat_backward_pass_camera(gsplat_context *c, const gsplat_gaussians *g, co
 int gsplat_context_set_depth(gsplat_context *c, int enabled) {
   GS_REQUIRE(c != nullptr, "null context");
   c->depth = enabled != 0;
+  return GSPLAT_OK;
+}
+
+int gsplat_context_set_absgrad(gsplat_context *c, int enabled) {
+  GS_REQUIRE(c != nullptr, "null context");
+  c->absgrad = enabled != 0;  // (read by the next compositing backward; the forward has no part in it)
+  return GSPLAT_OK;
+}
+
+int gsplat_context_absgrad_uv(gsplat_context *c, float *abs_uv, void *stream) {
+  GS_REQUIRE(c != nullptr, "null context");
+  GS_REQUIRE(!c->render_only, "a render-only context has no backward");
+  GS_REQUIRE(c->have_forward && c->rows_ready, "no compositing backward since the last forward");
+  GS_REQUIRE(c->rows_abs, "the last compositing backward did not run in absgrad mode (gsplat_context_set_absgrad)");
+  if (c->M == 0) return GSPLAT_OK;
+  GS_REQUIRE_DEV(abs_uv);
+  GS_REQUIRE(((uintptr_t)abs_uv & 7) == 0, "abs_uv must be 8-byte aligned");
+  copy_abs_uv_kernel<<<gs::div_up((long long)c->M, kBlock), kBlock, 0, (hipStream_t)stream>>>(
+      c->grad_rows.as<float4>(), c->M, reinterpret_cast<float2 *>(abs_uv));
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int gsplat_pack_absgrad_norm(gsplat_context *c, int num_gaussians, float *uv_norm, void *stream) {
+  GS_REQUIRE(c != nullptr, "null context");
+  GS_REQUIRE(!c->render_only, "a render-only context has no backward");
+  GS_REQUIRE(c->have_forward && c->rows_ready, "no compositing backward since the last forward");
+  GS_REQUIRE(c->rows_abs, "the last compositing backward did not run in absgrad mode (gsplat_context_set_absgrad)");
+  GS_REQUIRE(num_gaussians == c->N, "does not match the recorded forward");
+  GS_REQUIRE_DEV(uv_norm);
+  pack_abs_norm_kernel<<<gs::div_up((long long)num_gaussians, kBlock), kBlock, 0, (hipStream_t)stream>>>(
+      c->mask.as<unsigned char>(), c->rank.as<int>(), num_gaussians, c->grad_rows.as<float4>(), uv_norm);
+  GS_LAUNCH_CHECK();
   return GSPLAT_OK;
 }
 

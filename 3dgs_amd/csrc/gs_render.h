@@ -441,6 +441,57 @@ __device__ __host__ __forceinline__ int row_moments9r_index(int lane) {
   return j < 3 ? j : j == 4 ? 3 : j == 5 ? 4 : j == 6 ? 6 : j == 8 ? 5 : j == 9 ? 7 : j == 11 ? 8 : -1;
 }
 
+// ---- absgrad mode (gsplat_context_set_absgrad): the same sums plus the row totals of two per-pixel ABSOLUTE values,
+//   U = |gp| |pu|,  V = |gp| |pv|,   (pu, pv) = (2 a2 dx + b2 dy, 2 c2 dy + b2 dx)  in the staged conic (stage_record),
+// i.e. |d/du| and |d/dv| of this pixel's share up to the per-gaussian factor -kConicOff x (0.5 W | 0.5 H) the flush
+// applies.  They cannot ride in the quad stage's v_fmac_dpp (neither factor is a lane constant), so they take the
+// masked-bank route of row_sum9: lanes 4 apart fold U | V into one register (banks 0,2 | 1,3: 2 instructions), lanes 8
+// apart one rotate, then the two quad steps -- 2 products + 5 DPP adds.  Bank 2 ends with U's total in every lane, bank 3
+// with V's; one v_cndmask parks them in the two lanes of the totals' register that carry nothing (lane 10: Q's zero
+// weight, lane 12: bank 3), so the ONE LDS atomic of the trip adds them too.  10 VALU on top of row_moments9r's 14, no
+// s_nop: every DPP read of U sits two instructions behind its write, with the colour / moment chain's instructions in
+// between; that chain is row_moments9r's, operation for operation (the nine sums are bit for bit those of the mode off).
+// The accumulators are twelve doubles per slot here: addr <- off * 6 + acc_lane.
+__device__ __forceinline__ float row_moments9r_abs(float aT, float gp, float pu, float pv, const RowsWeights &w, unsigned int off,
+                                                   unsigned int acc_lane, unsigned int &addr) {
+  float A, B, Q, U, V;
+  const unsigned long long park = 0x1400140014001400ull;  // lanes 10 and 12 of every row
+  asm volatile(
+      "v_mul_f32_e64 %[U], |%[gp]|, |%[pu]|\n\t"
+      "v_mul_f32_e64 %[V], |%[gp]|, |%[pv]|\n\t"
+      "v_mul_f32 %[A], %[aT], %[a0]\n\t"
+      "v_mul_f32 %[B], %[gp], %[b0]\n\t"
+      "v_fmac_f32_dpp %[A], %[aT], %[a1] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp %[B], %[gp], %[b1] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %[U], %[U], %[U] row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_add_f32_dpp %[U], %[V], %[V] row_shr:4 row_mask:0xf bank_mask:0xa bound_ctrl:0\n\t"
+      "v_fmac_f32_dpp %[A], %[aT], %[a2] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp %[B], %[gp], %[b2] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %[U], %[U], %[U] row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp %[A], %[aT], %[a3] quad_perm:[3,2,1,0] row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp %[B], %[gp], %[b3] quad_perm:[3,2,1,0] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %[U], %[U], %[U] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_mul_f32 %[Q], %[B], %[wq]\n\t"
+      "v_add_f32_dpp %[A], %[A], %[A] row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_add_f32_dpp %[U], %[U], %[U] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "v_add_f32_dpp %[A], %[B], %[B] row_shr:4 row_mask:0xf bank_mask:0xa bound_ctrl:0\n\t"
+      "v_add_f32_dpp %[Q], %[Q], %[Q] row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_mad_u32_u24 %[addr], %[off], 6, %[acc]\n\t"
+      "v_add_f32_dpp %[A], %[A], %[A] row_shl:8 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_add_f32_dpp %[A], %[Q], %[Q] row_shr:8 row_mask:0xf bank_mask:0xc bound_ctrl:0\n\t"
+      "v_cndmask_b32_e64 %[A], %[A], %[U], %[park]\n\t"
+      : [A] "=&v"(A), [B] "=&v"(B), [Q] "=&v"(Q), [U] "=&v"(U), [V] "=&v"(V), [addr] "=&v"(addr)
+      : [aT] "v"(aT), [gp] "v"(gp), [pu] "v"(pu), [pv] "v"(pv), [a0] "v"(w.a[0]), [a1] "v"(w.a[1]), [a2] "v"(w.a[2]),
+        [a3] "v"(w.a[3]), [b0] "v"(w.b[0]), [b1] "v"(w.b[1]), [b2] "v"(w.b[2]), [b3] "v"(w.b[3]), [wq] "v"(w.q),
+        [off] "v"(off), [acc] "v"(acc_lane), [park] "s"(park));
+  return A;
+}
+// row_moments9r_index plus the two parked totals: 10 = sum |gp pu|, 11 = sum |gp pv|
+__device__ __host__ __forceinline__ int row_moments9r_abs_index(int lane) {
+  const int j = lane & 15;
+  return j == 10 ? 10 : j == 12 ? 11 : row_moments9r_index(lane);
+}
+
 // Blocks are dealt round-robin over the 8 XCDs; give each XCD a contiguous run of tiles so
 // neighbouring tiles (which share gaussians) hit the same L2.  Returns >= num_tiles for the
 // padding blocks of the last round.

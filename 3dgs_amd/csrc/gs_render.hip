@@ -669,8 +669,13 @@ __device__ __forceinline__ int row_max_int(int v) {  // max over the 16 lanes of
 #ifndef GS_BWD_DEPTH_WAVES
 #define GS_BWD_DEPTH_WAVES 7
 #endif
-template <bool kPacked, bool kRows, int kB, bool kDepth = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDepth ? GS_BWD_DEPTH_WAVES : 8, 8))) void render_bwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
+// waves per SIMD the absgrad instantiations are compiled for (gsplat_context_set_absgrad; gs_render.h: row_moments9r_abs):
+// their twelve accumulators per slot make 22.5 KB of LDS per workgroup, seven workgroups per CU whatever the registers
+#ifndef GS_BWD_ABS_WAVES
+#define GS_BWD_ABS_WAVES 7
+#endif
+template <bool kPacked, bool kRows, int kB, bool kDepth = false, bool kAbs = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_BWD_ABS_WAVES : kDepth ? GS_BWD_DEPTH_WAVES : 8, 8))) void render_bwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
                                                               const int *__restrict__ sorted,
                                                               const int *__restrict__ ranges,
                                                               const int *__restrict__ n_px,
@@ -682,12 +687,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDepth ? GS
                                                               DepthMaps dm) {
   static_assert(kPacked || !kDepth, "depth mode is a mode of the context's (packed) kernels");
   static_assert(!kDepth || GS_ROWSUM_QUAD == 2, "the tenth sum rides in row_moments9r's colour register");
+  static_assert(!kAbs || (kPacked && kRows && GS_ROWSUM_QUAD == 2 && GS_BWD_ALPHA_ASM == 1),
+                "absgrad mode is a mode of the context's kernel in its default loop form (row slots 10 and 11)");
   __shared__ float4 s_r0[kB + 1], s_r1[kB + 1];  // [kB]: the all-zero sentinel record
   // [slot][9]: rgb, S0, Sx, Sy, Sxx, Sxy, Syy.  Doubles on purpose: on gfx950 ds_add_f32 retires about one LANE
   // every three cycles while ds_add_f64 runs at LDS rate (profiles/microbench/lds_atomic_rate: 109 vs 16 cycles for
   // a 36-lane instruction), and the merge across the tile's 16 blocks needs one atomic per trip.
-  constexpr int kAcc = 10;  // doubles per slot (nine used, ten in depth mode): 80 bytes = 5 x the list entry's byte offset
-  constexpr int kRes = kDepth ? 10 : 9;  // gradient values per gaussian: row slots 0..8 (depth mode: and slot 9, dL/dz)
+  // doubles per slot (nine used, ten in depth mode): 80 bytes = 5 x the list entry's byte offset; absgrad mode: twelve, 6 x
+  constexpr int kAcc = kAbs ? 12 : 10;
+  // gradient values per gaussian: row slots 0..8 (depth mode: and slot 9, dL/dz; absgrad mode: and 10, 11, sum |d/du|, |d/dv|)
+  constexpr int kRes = kAbs ? 12 : kDepth ? 10 : 9;
   __shared__ double s_acc[(kB + 1) * kAcc];  // slot kB: the sentinel's (rows past the end of their list add zeros there)
   __shared__ int s_id[kB];
   // row lists | third record array; both are dead once the batch's trips are done, and the flush parks the nine
@@ -805,7 +814,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDepth ? GS
   // pixel position relative to the tile centre, pixel gradient
 #if GS_ROWSUM_QUAD == 2
   // (depth mode: lane 3 of the row holds the tenth sum, aT x dL/d depth: the fourth channel of the colour register)
-  const int red_idx = kDepth && (lane & 15) == 3 ? 9 : row_moments9r_index(lane);
+  const int red_idx = kDepth && (lane & 15) == 3 ? 9 : kAbs ? row_moments9r_abs_index(lane) : row_moments9r_index(lane);
 #elif GS_ROWSUM_QUAD
   const int red_idx = row_moments9q_index(lane);
 #else
@@ -955,7 +964,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDepth ? GS
           // read it -- the first FMA of the colour dot product, as ONE block: between separate asm statements the
           // compiler puts an s_nop per border (three per trip).
           float og, t0;
-          {
+          [[maybe_unused]] float pu = 0.0f, pv = 0.0f;  // (absgrad mode) this pixel's d power / d(u, v) in the staged conic
+          if constexpr (kAbs) {
+            // the same chain with the exponent in a register of its own, so that a2 dx + b2 dy and c2 dy outlive it: one
+            // FMA makes pu = 2 a2 dx + b2 dy of the first, two make pv = 2 c2 dy + b2 dx of the second
+            float qq;
+            asm("v_mul_f32 %[t], %[a2], %[dx]\n\t"
+                "v_mul_f32 %[u], %[c2], %[dy]\n\t"
+                "v_fmac_f32 %[t], %[b2], %[dy]\n\t"
+                "v_fma_f32 %[q], %[t], %[dx], %[lopa]\n\t"
+                "v_fmac_f32 %[q], %[u], %[dy]\n\t"
+                "v_min_f32 %[q], %[q], %[lopa]\n\t"
+                "v_exp_f32 %[og], %[q]\n\t"
+                "v_fma_f32 %[t0], %[cx], %[g0], -%[s]\n\t"
+                "v_fmac_f32 %[t], %[a2], %[dx]\n\t"
+                "v_fmac_f32 %[u], %[b2], %[dx]\n\t"
+                "v_fmac_f32 %[u], %[c2], %[dy]"
+                : [og] "=&v"(og), [t0] "=&v"(t0), [t] "=&v"(pu), [u] "=&v"(pv), [q] "=&v"(qq)
+                : [a2] "v"(a.z), [b2] "v"(a.w), [c2] "v"(b.x), [lopa] "v"(b.y), [dx] "v"(dx), [dy] "v"(dy), [cx] "v"(c.x),
+                  [g0] "v"(g0), [s] "v"(s));
+          } else {
             float tq, uq;
             asm("v_mul_f32 %[t], %[a2], %[dx]\n\t"
                 "v_mul_f32 %[u], %[c2], %[dy]\n\t"
@@ -1021,7 +1049,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDepth ? GS
 #else
 #if GS_ROWSUM_QUAD == 2
           unsigned int acc_addr;
-          const float red = row_moments9r(aT, gp, rw, (unsigned int)off, acc_lane, acc_addr);
+          float red;
+          if constexpr (kAbs) red = row_moments9r_abs(aT, gp, pu, pv, rw, (unsigned int)off, acc_lane, acc_addr);
+          else red = row_moments9r(aT, gp, rw, (unsigned int)off, acc_lane, acc_addr);
 #elif GS_ROWSUM_QUAD
           const float red = row_moments9q(aT, gp, rw);
           const unsigned int acc_addr = acc_lane + __umul24((unsigned int)off, 5u);
@@ -1092,6 +1122,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kDepth ? GS
       res[7] = keep * (-(ca * sx + cb * sy) * (0.5f * (float)width));                // u (render_backward.cu:180-186)
       res[8] = keep * (-(cc * sy + cb * sx) * (0.5f * (float)height));               // v (:181-187)
       if constexpr (kDepth) res[9] = keep * (float)acc[9];                            // dL/dz = sum aT dL/d depth
+      else if constexpr (kAbs) res[9] = 0.0f;
+      if constexpr (kAbs) {
+        // sum over the tile's pixels of |this pixel's share of d/du|, |.. d/dv|: ca dx + cb dy = kConicOff pu (stage_record)
+        res[10] = keep * ((float)acc[10] * -kConicOff * (0.5f * (float)width));
+        res[11] = keep * ((float)acc[11] * -kConicOff * (0.5f * (float)height));
+      }
     }
     GS_LAP(st_flush);
     __syncthreads();
@@ -1833,7 +1869,7 @@ int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorte
                       const float *T_px, const float *grad_image, int width, int height, float bg, float *rows,
                       float *g_rgb, float *g_opacity, float *g_uv, float *g_conic, hipStream_t st, const unsigned short *masks_in,
                       hipEvent_t ev_start, hipEvent_t ev_stop, const int *order, const TileSegments *segments,
-                      const DepthMaps *depth) {
+                      const DepthMaps *depth, bool absgrad) {
   const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
   const TileSegments seg = segments ? *segments : TileSegments{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
   // split lists: their further segments are extra blocks in front of the main grid (blocks beyond the count leave at once)
@@ -1844,7 +1880,22 @@ int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorte
   const int pingpong = pp_env ? atoi(pp_env) : GS_BWD_PINGPONG;
   const DepthMaps dm = depth ? *depth : DepthMaps{};
   GS_REQUIRE(!depth || (recs && rows), "depth mode needs the packed records and the gradient rows");
-  if (depth) {  // (gs_render.h: DepthMaps; the ping-pong experiment has no depth form: always the default loop)
+  GS_REQUIRE(!absgrad || (recs && rows), "absgrad mode needs the packed records and the gradient rows");
+  if (absgrad) {  // (gs_render.h: row_moments9r_abs; like depth mode always the default loop, with or without depth gradients)
+#define GS_ABS_LAUNCH(DEPTH)                                                                                              \
+  do {                                                                                                                    \
+    if (ev_start && ev_stop)                                                                                              \
+      hipExtLaunchKernelGGL((render_bwd_kernel<true, true, GS_BWD_BATCH, DEPTH, true>), grid, block, 0, st, ev_start, ev_stop, \
+                            0, recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out,  \
+                            masks_in, order, seg, dm);                                                                     \
+    else                                                                                                                  \
+      render_bwd_kernel<true, true, GS_BWD_BATCH, DEPTH, true><<<grid, block, 0, st>>>(                                    \
+          recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm); \
+  } while (0)
+    if (depth) GS_ABS_LAUNCH(true);
+    else GS_ABS_LAUNCH(false);
+#undef GS_ABS_LAUNCH
+  } else if (depth) {  // (gs_render.h: DepthMaps; the ping-pong experiment has no depth form: always the default loop)
     if (ev_start && ev_stop)
       hipExtLaunchKernelGGL((render_bwd_kernel<true, true, GS_BWD_BATCH, true>), grid, block, 0, st, ev_start, ev_stop, 0, recs,
                             none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order,
@@ -1983,7 +2034,7 @@ int gsplat_render_image_backward(const float *uvs, const float *opacity, const f
     GS_HIP(hipMemsetAsync(rows.ptr, 0, (size_t)bound * 64, st));
     rc = gs::launch_render_bwd(nullptr, &raw, sorted_splats, splat_range_by_tile, num_splats_per_pixel,
                                final_weight_per_pixel, grad_image, image_width, image_height, background_opacity,
-                               rows.as<float>(), nullptr, nullptr, nullptr, nullptr, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+                               rows.as<float>(), nullptr, nullptr, nullptr, nullptr, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false);
     if (rc) return rc;
     rows_to_arrays_kernel<<<gs::div_up(bound, 256), 256, 0, st>>>(rows.as<float4>(), bound, grad_rgb, grad_opacity, grad_uv,
                                                                   grad_conic);
@@ -1992,7 +2043,7 @@ int gsplat_render_image_backward(const float *uvs, const float *opacity, const f
   }
   return gs::launch_render_bwd(nullptr, &raw, sorted_splats, splat_range_by_tile, num_splats_per_pixel,
                                final_weight_per_pixel, grad_image, image_width, image_height, background_opacity,
-                               nullptr, grad_rgb, grad_opacity, grad_uv, grad_conic, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+                               nullptr, grad_rgb, grad_opacity, grad_uv, grad_conic, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false);
 }
 
 }  // extern "C"

@@ -200,6 +200,28 @@ def parseConfig(path):
     return out
 
 
+# keys this project adds to the flat `key: value` file; optional (ConfigParameters and its parser stay the reference's)
+EXTENSION_KEYS = dict(absgrad=False)
+
+
+def parseExtensions(path):
+    """The optional keys of EXTENSION_KEYS a configuration file carries, as a dict (booleans spelled as the parser's).
+    gsplat_parse_config ignores keys it does not know, so a file with them still parses as ConfigParameters."""
+    out = {}
+    with open(path) as f:
+        for line in f:
+            k, sep, v = line.split("#", 1)[0].partition(":")
+            k, v = k.strip(), v.strip().strip("'\"")
+            if sep and k in EXTENSION_KEYS:
+                if v in ("true", "True", "TRUE", "yes", "on"):
+                    out[k] = True
+                elif v in ("false", "False", "FALSE", "no", "off"):
+                    out[k] = False
+                else:
+                    raise HostError(-1, f"{path}: {k} is not a boolean: {v}")
+    return out
+
+
 def save_ply(path, xyz, rgb, opacity, scale, quaternion, sh=None):
     """quaternion [N,4] as (w,x,y,z); sh [N,k] flattened per gaussian or None (src/utils.cpp:89-175)."""
     f = lambda a, w: np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, w)) if w else None

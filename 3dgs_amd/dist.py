@@ -377,10 +377,14 @@ class ViewShardedStep:
     with_uv_norm=True (training): the all-reduced buffer carries N more floats, the per-view |grad_uv| in global
     order, so that after the exchange `uv_norm_sum[N]` holds the sum over the step's views: what the densification
     statistics of cuda/trainer.cu:1136-1157 need on a view-sharded step.  Same collective, no extra launch on the wire.
+
+    absgrad=True: the step switches its context to absgrad mode (RasterContext.set_absgrad; False switches it off) and
+    the per-view statistic is absnorm, the norm of the absolute sums of the pixels' shares of grad_uv, on every payload:
+    `uv_norm_sum` is then the sum of absnorm over the ranks.  The gradients are the same either way.
     """
 
     def __init__(self, params, l_max, width, height, config, bg, exchange="split", with_uv_norm=False, ctx=None,
-                 comm=None, chunks=None, exchange_at_world_one=False):
+                 comm=None, chunks=None, exchange_at_world_one=False, absgrad=False):
         from . import raster
         self.raster = raster
         self.params, self.l_max, self.config, self.bg = params, l_max, config, bg
@@ -392,6 +396,8 @@ class ViewShardedStep:
             ctx = raster.RasterContext(N, width, height)
             ctx.set_lean_forward(True)
         self.ctx = ctx
+        self.absgrad = bool(absgrad)
+        ctx.set_absgrad(self.absgrad)
         self.width_cols = wc = raster.packed_gradient_width(l_max)
         self.dev = dev = params["xyz"].device
         self.comm = comm if comm is not None else TorchComm()  # ThreadComm: in-process ranks (ThreadGroup)
@@ -535,6 +541,8 @@ class ViewShardedStep:
             return None
         if self._blind:
             self._reduce_buf.zero_()
+        elif self.with_uv_norm and self.absgrad:
+            self.raster.pack_absgrad_norm(self.ctx, N, self.uv_norm_sum)
         elif self.with_uv_norm:
             self.raster.pack_uv_grad_norm(self.ctx, self.grads, N, self.uv_norm_sum)
         if self.exchange == "factored":

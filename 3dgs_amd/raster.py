@@ -171,6 +171,23 @@ class RasterContext:
         check(self._lib.gsplat_context_set_depth(self._h, int(bool(enabled))))
         self._depth = bool(enabled)
 
+    def set_absgrad(self, enabled):
+        """Absgrad mode (gsplat_context_set_absgrad): from the next backward_render / backward_pass on, the compositing
+        backward also sums every pixel's share of dL/d uv by absolute value, and the densification statistics (uv_norm
+        of the split form, uv_grad_accum of the fused Adam forms) are the norm of those sums instead of |grad_uv|.  Every
+        gradient is unchanged."""
+        check(self._lib.gsplat_context_set_absgrad(self._h, int(bool(enabled))))
+
+    def absgrad_uv(self):
+        """abs_uv [M,2] of the last compositing backward (compacted order): (sum_p |du_p|, sum_p |dv_p|) over the pixels'
+        shares of grad_uv.  Valid until the next forward; an error unless that backward ran in absgrad mode
+        (gsplat_context_absgrad_uv)."""
+        M = self._last[1] if self._last else 0
+        out = torch.empty(M, 2, dtype=torch.float32, device="cuda")
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self._lib.gsplat_context_absgrad_uv(self._h, _ptr(out), st))
+        return out
+
     def set_preprocess_split(self, mode):
         """How the per-gaussian forward is launched: 0 (default) the single fused kernel, 1 SH colour then geometry on the
         caller's stream, 2 the two side by side on two streams (gsplat_context_set_preprocess_split); every output is
@@ -424,6 +441,14 @@ def pack_uv_grad_norm(ctx, grads, num_gaussians, uv_norm):
     gs = RasterContext._grad_struct(grads)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     check(_lib.load().gsplat_pack_uv_grad_norm(ctx._h, ctypes.byref(gs), int(num_gaussians), _ptr(uv_norm), st))
+    return uv_norm
+
+
+def pack_absgrad_norm(ctx, num_gaussians, uv_norm):
+    """This view's absnorm = |(sum_p |du_p|, sum_p |dv_p|)| in global gaussian order (0 where culled), after a compositing
+    backward in absgrad mode: gsplat_pack_absgrad_norm, the counterpart of pack_uv_grad_norm."""
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    check(_lib.load().gsplat_pack_absgrad_norm(ctx._h, int(num_gaussians), _ptr(uv_norm), st))
     return uv_norm
 
 

@@ -27,7 +27,10 @@ DEFAULT_CONFIG = dict(
     use_background_end=2000, reset_opacity_interval=3000, reset_opacity_value=0.05, reset_opacity_start=1050,
     reset_opacity_end=5000, max_sh_band=3, add_sh_band_interval=1000, use_split=True, use_clone=True, use_delete=True,
     adaptive_control_start=500, adaptive_control_end=5000, adaptive_control_interval=100, max_gaussians=4250000,
-    delete_opacity_threshold=0.02, uv_grad_threshold=0.0002, split_scale_factor=1.6)
+    delete_opacity_threshold=0.02, uv_grad_threshold=0.0002, split_scale_factor=1.6,
+    # absgrad: uv_grad_accum sums, per view, the norm of the ABSOLUTE sums of the pixels' shares of grad_uv instead of
+    # |grad_uv| (RasterContext.set_absgrad); uv_grad_threshold is compared as given and has to be raised with it (README)
+    absgrad=False)
 
 
 def _logit(p):
@@ -91,6 +94,7 @@ class Trainer:
         H = max(int(c["height"]) for c, _ in views)
         self.ctx = raster.RasterContext(max(n, 1), W, H)
         self.ctx.set_lean_forward(True)  # the loop only runs the fused backward, which recomputes Sigma / J / conic
+        self.ctx.set_absgrad(bool(self.cfg["absgrad"]))
         self.ctx_capacity = n
         self._new_optimizer(None)
         self.history = []
@@ -117,6 +121,7 @@ class Trainer:
             W, H = self.ctx.max_width, self.ctx.max_height
             self.ctx = raster.RasterContext(self.ctx_capacity, W, H)
             self.ctx.set_lean_forward(True)
+            self.ctx.set_absgrad(bool(self.cfg["absgrad"]))
         return self.ctx
 
     # ------------------------------------------------------------------ one iteration (cuda/trainer.cu:1338-1362)
@@ -180,6 +185,8 @@ class Trainer:
         else:
             grads = self._gradients_for(ctx, fwd["num_culled"])
             ctx.backward_pass(p, cam, grad_image, bg, self.l_max, grads)
+            if c["absgrad"]:  # the optimizer kernel takes the norm of what it is given as grad_uv: the absolute sums
+                grads = dict(grads, uv=ctx.absgrad_uv())
             self.opt.step(it, fwd, grads, campos=cam["campos"])
         self.iter += 1
         return loss
@@ -198,7 +205,8 @@ class Trainer:
             ctx = self._context_for(n)
             p = dict(self.params)
             self._sharded = (key, ViewShardedStep(p, self.l_max, ctx.max_width, ctx.max_height, c, 0.0,
-                                                  exchange=self.exchange, with_uv_norm=True, ctx=ctx, comm=self.comm))
+                                                  exchange=self.exchange, with_uv_norm=True, ctx=ctx, comm=self.comm,
+                                                  absgrad=bool(c["absgrad"])))
         step = self._sharded[1]
         H, W = int(cam["height"]), int(cam["width"])
         out = {}

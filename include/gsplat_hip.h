@@ -655,6 +655,30 @@ int gsplat_unpack_gradients_split(const float *xyz, const float *common, const f
 int gsplat_pack_uv_grad_norm(gsplat_context *ctx, const gsplat_gradients *grads, int num_gaussians, float *uv_norm,
                              void *stream);
 
+/* Absolute screen-space gradients ("absgrad") for densification.  grad_uv[j] is the SIGNED sum over the pixels p that
+ * composite gaussian j of the pixel's share (du_p, dv_p) of dL/d uv (render_image_backward adds exactly these, the
+ * 0.5 W / 0.5 H factors and, with depth gradients, the depth and alpha terms included); on a large blurry splat the
+ * shares of opposite sides cancel and |grad_uv| never reaches the threshold.  In absgrad mode the compositing backward
+ * also forms
+ *   abs_uv[j] = ( sum_p |du_p| , sum_p |dv_p| ),      absnorm[j] = sqrtf(abs_u^2 + abs_v^2)  >=  |grad_uv[j]|,
+ * and every densification statistic the library writes -- uv_norm of gsplat_backward_render_split /
+ * gsplat_backward_gaussians_split, uv_grad_accum of gsplat_backward_gaussians_adam (modes 0, 1, 2) -- is absnorm instead
+ * of |grad_uv|.  grad_uv itself and every gradient array are what they are with the mode off.
+ *   gsplat_context_set_absgrad  a mode of the context (default 0), read by the next gsplat_backward_render* call; it asks
+ *                               nothing of the forward: training, lean and depth forwards alike;
+ *   gsplat_context_absgrad_uv   abs_uv[M,2] (compacted order, 8-byte aligned) of the last compositing backward.
+ *                               GSPLAT_ERR_INVALID_ARG before anything is launched when that backward did not run in
+ *                               absgrad mode, when there has been none since the last forward, or when the context is
+ *                               render-only;
+ *   gsplat_pack_absgrad_norm    uv_norm[N] = absnorm in global gaussian order, 0 where the view culled the gaussian: what
+ *                               gsplat_pack_uv_grad_norm is to |grad_uv|, for hosts that keep the unfused path.  The same
+ *                               refusals.
+ * The sums live in the context's gradient rows: they are valid from the compositing backward until the next forward of
+ * the context (which clears the rows), whichever per-gaussian calls run in between. */
+int gsplat_context_set_absgrad(gsplat_context *ctx, int enabled);
+int gsplat_context_absgrad_uv(gsplat_context *ctx, float *abs_uv, void *stream);
+int gsplat_pack_absgrad_norm(gsplat_context *ctx, int num_gaussians, float *uv_norm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

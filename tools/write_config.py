@@ -25,6 +25,7 @@ ORDER = ("dataset_path downsample_factor output_dir print_interval test_eval_int
          "max_sh_band add_sh_band_interval reset_opacity_interval reset_opacity_value reset_opacity_start reset_opacity_end "
          "use_split use_clone use_delete adaptive_control_start adaptive_control_end adaptive_control_interval max_gaussians "
          "delete_opacity_threshold uv_grad_threshold split_scale_factor").split()
+EXTENSIONS = ("absgrad",)  # optional keys behind ConfigParameters' (3dgs_amd/dataset.py: EXTENSION_KEYS)
 
 
 def main():
@@ -35,15 +36,19 @@ def main():
         args.remove("--extended")
         cfg.update(print_interval=500, num_iters=30000, use_background_end=10000, reset_opacity_end=15000,
                    adaptive_control_end=15000)
+    given = set()
     for kv in args:
         k, v = kv.split("=", 1)
         if k not in cfg:
             raise SystemExit(f"unknown key {k}")
         cfg[k] = v
+        given.add(k)
     fmt = lambda v: ("true" if v else "false") if isinstance(v, bool) else str(v)
+    # this project's optional keys (dataset.EXTENSION_KEYS, e.g. absgrad=true) are written only when they are given
+    extra = [k for k in EXTENSIONS if k in given]
     with open(sys.argv[1], "w") as f:
-        f.write("".join(f"{k}: {fmt(cfg[k])}\n" for k in ORDER))
-    print(f"wrote {len(ORDER)} keys to {sys.argv[1]}")
+        f.write("".join(f"{k}: {fmt(cfg[k])}\n" for k in list(ORDER) + extra))
+    print(f"wrote {len(ORDER) + len(extra)} keys to {sys.argv[1]}")
 
 
 if __name__ == "__main__":
