@@ -217,6 +217,9 @@ SIGNATURES = {
     "gsplat_context_set_absgrad": (_I, [_P, _I]),
     "gsplat_context_absgrad_uv": (_I, [_P, _P, _P]),
     "gsplat_pack_absgrad_norm": (_I, [_P, _I, _P, _P]),
+    "gsplat_context_set_antialiased": (_I, [_P, _I]),
+    "gsplat_compute_conic_antialiased": (_I, [_P, _P, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "gsplat_compute_conic_antialiased_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "gsplat_context_set_preprocess_split": (_I, [_P, _I]),
     "gsplat_context_get_counters": (_I, [_P, ctypes.POINTER(ctypes.c_longlong), _I]),
     "gsplat_context_set_timing": (_I, [_P, _I]),

@@ -107,6 +107,11 @@ struct gsplat_context {
   // value, into row slots 10 and 11 (gs_render.h: row_moments9r_abs); the densification statistics are made of those
   bool absgrad = false;
   bool rows_abs = false;  // the gradient rows carry those sums (the last compositing backward ran in absgrad mode)
+  // anti-aliased mode (gsplat_context_set_antialiased): the forward's records carry sigmoid(logit) * rho, rho the opacity
+  // compensation for the 0.3 px blur (gs_math.h: conic_radius<true>); the per-gaussian backward of that forward turns
+  // row slot 3 into dL/d logit and the covariance term of dL/d rho
+  bool antialiased = false;
+  bool fwd_antialiased = false;  // the recorded forward ran in the mode (its backwards follow it, whatever is set by then)
   void *fseg_gran_zeroed = nullptr;  // the granule block whose tags have been cleared (a fresh block holds anything)
   size_t fseg_gran_zeroed_bytes = 0;
   unsigned int fseg_epoch = 0;
@@ -367,7 +372,9 @@ struct PreOut {
 //     (r02: 23 % of HBM on such a view).
 // Everything a gaussian stores leaves BEFORE its tile loop, which then holds six numbers per lane: kept across the loop,
 // Sigma, J, conic, colour and the 48-byte record pushed the SH-3 instance past its 128 registers (6 spilled in r02).
-template <int L, bool kStoreMid, bool kCompact>
+//   kAntialias (gsplat_context_set_antialiased): the record's opacity is sigmoid(logit) * rho; conic, radii and tile tests
+//     are what they are without the flag -- a template flag, so that the default instantiations stay exactly what they were
+template <int L, bool kStoreMid, bool kCompact, bool kAntialias = false>
 __global__ __launch_bounds__(gs::kBinThreads) void preprocess_kernel(gsplat_gaussians g, const float *__restrict__ view,
                                                             const unsigned char *__restrict__ mask,
                                                             int *__restrict__ rank,
@@ -485,12 +492,18 @@ __global__ __launch_bounds__(gs::kBinThreads) void preprocess_kernel(gsplat_gaus
       gs::to_screen(gs::load_proj(proj), x, y, z, width, height, u, v);
     }
     gs::jacobian(x, y, z, fx, fy, tan_fovx, tan_fovy, J);
-    gs::conic_radius(J, sg, vw, mh_dist, con, rad);
+    [[maybe_unused]] float rho = 1.0f, cov_raw[3];
+    if constexpr (kAntialias) gs::conic_radius<true>(J, sg, vw, mh_dist, con, rad, &rho, cov_raw);
+    else gs::conic_radius(J, sg, vw, mh_dist, con, rad);
     // stores (compacted order); counts and hitmask follow the tile tests
     o.c2g[j] = i;
     o.uv[2 * j] = u; o.uv[2 * j + 1] = v;
     reinterpret_cast<float4 *>(o.radius)[j] = make_float4(rad[0], rad[1], rad[2], rad[3]);
-    const gs::SplatRec rec = gs::make_record(u, v, con[0], con[1], con[2], g.opacity[i], rgb[0], rgb[1], rgb[2]);
+    gs::SplatRec rec;
+    if constexpr (kAntialias)
+      rec = gs::make_record_opa(u, v, con[0], con[1], con[2], gs::sigmoid_fast(g.opacity[i]) * rho, rgb[0], rgb[1], rgb[2]);
+    else
+      rec = gs::make_record(u, v, con[0], con[1], con[2], g.opacity[i], rgb[0], rgb[1], rgb[2]);
     if constexpr (kStoreMid) {
       const float xyzc[3] = {x, y, z};
       wave_rows_store<3>(o.xyz_c, j0, pp, nact, xyzc, wsh);
@@ -1043,7 +1056,12 @@ struct AdamFused {
 // gsplat_context_set_absgrad), and the densification statistic -- uv_norm of the split form, uv_grad_accum of the Adam
 // forms -- is their norm instead of |grad_uv|; every gradient is what it is without the flag.  (The camera form stores no
 // statistic and has no such instantiation.)
-template <int L, int kAdam = 0, bool kDepthRow = false, bool kCamGrad = false, bool kAbsRow = false>
+// kAntialias (plain form only; gsplat_context_set_antialiased): the recorded forward's records carried o = sigmoid(logit) *
+// rho, so row slot 3 is g_eff = dL/d logit(o).  rho is recomputed with the forward's function on the forward's inputs (bit
+// for bit its value, like Sigma, J and the conic); g_eff becomes dL/d logit and dL/d rho (gs::effective_opacity_bwd), and
+// dL/d rho enters conic_bwd as a covariance term (gs::compensation_bwd) -- dJ, dSigma and everything behind them take it
+// through the code that is there.
+template <int L, int kAdam = 0, bool kDepthRow = false, bool kCamGrad = false, bool kAbsRow = false, bool kAntialias = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam == 3 ? GS_BWD3_WAVES : 3, 8))) void preprocess_bwd_kernel(gsplat_gaussians g, const float *__restrict__ view,
                                                                 const float *__restrict__ proj, int M,
                                                                 const int *__restrict__ c2g,
@@ -1056,6 +1074,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
                                                                 double *__restrict__ cam_rows) {
   static_assert(!kCamGrad || kAdam == 0, "the camera gradient is a form of the plain backward");
   static_assert(!(kCamGrad && kAbsRow), "the camera form stores no densification statistic");
+  static_assert(!kAntialias || (kAdam == 0 && !kCamGrad), "anti-aliased mode is a form of the plain backward");
   // ranged: only the gaussians with global index in [i_lo, i_hi), i.e. the compacted slots [first slot whose global index
   // is >= i_lo, first slot whose global index is >= i_hi) (chunked backward of a view-sharded step: the exchange of one
   // chunk runs while the next is computed); the grid covers the largest possible chunk, blocks past its end leave at once.
@@ -1269,9 +1288,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
     gs::sigma_from(rs, sg);
   }
   gs::jacobian(x, y, z, fx, fy, fwd_tan_fovx, fwd_tan_fovy, Jv);
-  gs::conic_radius(Jv, sg, vw, mh_dist, con, rad_unused);
   float dM[kCamGrad ? 6 : 1];
-  gs::conic_bwd<kCamGrad>(Jv, sg, vw, con, g_con, dJ, dS, dM);
+  [[maybe_unused]] float g_logit = g_op;  // what the opacity's gradient array gets (kAntialias: its share of g_eff)
+  if constexpr (kAntialias) {
+    float rho, cov_raw[3], drho, dcov[3];
+    gs::conic_radius<true>(Jv, sg, vw, mh_dist, con, rad_unused, &rho, cov_raw);
+    gs::effective_opacity_bwd(g_op, gs::sigmoid_fast(g.opacity[i]), rho, g_logit, drho);
+    gs::compensation_bwd(cov_raw, rho, drho, dcov);
+    gs::conic_bwd<false, true>(Jv, sg, vw, con, g_con, dJ, dS, nullptr, dcov);
+  } else {
+    gs::conic_radius(Jv, sg, vw, mh_dist, con, rad_unused);
+    gs::conic_bwd<kCamGrad>(Jv, sg, vw, con, g_con, dJ, dS, dM);
+  }
 #pragma unroll
   for (int k = 0; k < 6; ++k) { dJ[k] = 0.0f + dJ[k]; dS[k] = 0.0f + dS[k]; }
   [[maybe_unused]] float jt_dm[kCamGrad ? 9 : 1];  // dL/dW through M = J W: (J^T dM)[r][c]
@@ -1333,13 +1361,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
       if (o.quaternion) reinterpret_cast<float4 *>(o.quaternion)[j] = make_float4(dQ[0], dQ[1], dQ[2], dQ[3]);
     } else if (o.common) {  // the exchange's row, in global order (the same twelve values pack_split_kernel gathers)
       gs::f4u *row = reinterpret_cast<gs::f4u *>(o.common + (size_t)i * 12);
-      row[0] = gs::f4u{gx, gy, gz, g_op};
+      row[0] = gs::f4u{gx, gy, gz, kAntialias ? g_logit : g_op};
       row[1] = gs::f4u{dSc[0], dSc[1], dSc[2], dQ[0]};
       row[2] = gs::f4u{dQ[1], dQ[2], dQ[3], 1.0f};
       if (o.uv_norm) o.uv_norm[i] = sqrtf(n_u * n_u + n_v * n_v);  // pack_uv_norm_kernel's expression
     } else {
       o.xyz[3 * j] = gx; o.xyz[3 * j + 1] = gy; o.xyz[3 * j + 2] = gz;
-      o.opacity[j] = g_op;
+      o.opacity[j] = kAntialias ? g_logit : g_op;
       o.scale[3 * j] = dSc[0]; o.scale[3 * j + 1] = dSc[1]; o.scale[3 * j + 2] = dSc[2];
       reinterpret_cast<float4 *>(o.quaternion)[j] = make_float4(dQ[0], dQ[1], dQ[2], dQ[3]);
     }
@@ -1978,6 +2006,8 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
   GS_REQUIRE_DEV(g->quaternion); GS_REQUIRE_DEV(cam->view); GS_REQUIRE_DEV(cam->proj);
   if (l_max > 0) GS_REQUIRE_DEV(g->sh);
   GS_REQUIRE(((uintptr_t)g->quaternion & 15) == 0, "quaternion must be 16-byte aligned");
+  GS_REQUIRE(!(c->antialiased && c->pre_split),
+             "anti-aliased mode has no two-kernel forward (gsplat_context_set_preprocess_split / GSPLAT_PRE_SPLIT must be 0)");
   hipStream_t st = (hipStream_t)stream;
   c->have_forward = false;
   c->rows_ready = false;
@@ -2066,13 +2096,15 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
   }
   const size_t hist_bytes = sparse ? (size_t)num_tiles * sizeof(int) : 0;
 #define GS_PRE3(LL, MID, CMP)                                                                                          \
-  preprocess_kernel<LL, MID, CMP><<<gs::kBinBlocks, gs::kBinThreads, hist_bytes, st>>>(                                \
+  if (c->antialiased) GS_PRE4(LL, MID, CMP, true); else GS_PRE4(LL, MID, CMP, false)
+#define GS_PRE4(LL, MID, CMP, AA)                                                                                      \
+  preprocess_kernel<LL, MID, CMP, AA><<<gs::kBinBlocks, gs::kBinThreads, hist_bytes, st>>>(                            \
       *g, cam->view, c->mask.as<unsigned char>(), c->rank.as<int>(), c->slice_counts(), c->kept.as<int>(),              \
       cam->proj, W, H, fx, fy, tan_fovx, tan_fovy, cfg->mh_dist, cam->campos[0], cam->campos[1], cam->campos[2], ntx, nty, po, bin_table)
 #define GS_PRE(LL)                                                                                                     \
   do {                                                                                                                 \
-    if (mid) { if (compact) GS_PRE3(LL, true, true); else GS_PRE3(LL, true, false); }                                  \
-    else { if (compact) GS_PRE3(LL, false, true); else GS_PRE3(LL, false, false); }                                    \
+    if (mid) { if (compact) { GS_PRE3(LL, true, true); } else { GS_PRE3(LL, true, false); } }                          \
+    else { if (compact) { GS_PRE3(LL, false, true); } else { GS_PRE3(LL, false, false); } }                            \
   } while (0)
   bool join_pending = false;
   if (c->pre_split) {
@@ -2140,7 +2172,9 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
   }
 #undef GS_PRE
 #undef GS_PRE3
+#undef GS_PRE4
   GS_LAUNCH_CHECK();
+  c->fwd_antialiased = c->antialiased;
   size_t inst_cap = 0;
   // the one host read-back of the forward: M, S (and the candidate count)
   const unsigned long long ticket = ++c->ticket;
@@ -2548,6 +2582,9 @@ int gsplat_backward_gaussians_split(gsplat_context *c, const gsplat_gaussians *g
 int gsplat_backward_gaussians_adam(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
                                    const gsplat_adam_fused *opt, const gsplat_gradients *out, void *stream) {
   GS_REQUIRE(opt != nullptr && g != nullptr, "null argument struct");
+  GS_REQUIRE(!(c && c->have_forward && c->fwd_antialiased),
+             "the forward ran in anti-aliased mode: the Adam-inside backward steps the opacity before the covariance chain "
+             "exists (use gsplat_backward_gaussians and the optimizer kernels)");
   const int n_groups = l_max > 0 ? 6 : 5;
   for (int k = 0; k < 6; ++k) {
     if (k == 2 && l_max == 0) continue;  // no coefficients beyond band 0
@@ -2607,6 +2644,10 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
   GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
              "backward arguments do not match the recorded forward pass");
   const bool cam_grad = grad_view != nullptr;  // gsplat_backward_gaussians_camera: whole range, plain form
+  GS_REQUIRE(!(c->fwd_antialiased && adam),
+             "the forward ran in anti-aliased mode: the Adam-inside backward steps the opacity before the covariance chain "
+             "exists (use gsplat_backward_gaussians and the optimizer kernels)");
+  GS_REQUIRE(!(c->fwd_antialiased && cam_grad), "the forward ran in anti-aliased mode: the camera gradient has no such form");
   if (cam_grad) {
     GS_REQUIRE_DEV(grad_view); GS_REQUIRE_DEV(grad_campos);
     GS_REQUIRE(!adam && !common && first_gaussian == 0 && end_gaussian == g->num_gaussians, "internal: camera form");
@@ -2667,6 +2708,8 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
       preprocess_bwd_kernel<LL, 2, DR, false, AB><<<grid, block, 0, st>>> GS_BWD_ARGS(*adam, nullptr);                 \
     else if (cam_grad) /* (stores no statistic: one form for both) */                                                  \
       preprocess_bwd_kernel<LL, 0, DR, true><<<grid, block, 0, st>>> GS_BWD_ARGS(kNoAdam, c->cam_rows.as<double>());   \
+    else if (c->fwd_antialiased)                                                                                       \
+      preprocess_bwd_kernel<LL, 0, DR, false, AB, true><<<grid, block, 0, st>>> GS_BWD_ARGS(kNoAdam, nullptr);         \
     else                                                                                                               \
       preprocess_bwd_kernel<LL, 0, DR, false, AB><<<grid, block, 0, st>>> GS_BWD_ARGS(kNoAdam, nullptr);               \
   } while (0)
@@ -2737,6 +2780,7 @@ int gsplat_backward_pass_camera(gsplat_context *c, const gsplat_gaussians *g, co
   GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
              "backward arguments do not match the recorded forward pass");
   GS_REQUIRE_DEV(grad_view); GS_REQUIRE_DEV(grad_campos);
+  GS_REQUIRE(!c->fwd_antialiased, "the forward ran in anti-aliased mode: the camera gradient has no such form");
   if (out) {
     GS_REQUIRE_DEV(out->grad_xyz); GS_REQUIRE_DEV(out->grad_rgb); GS_REQUIRE_DEV(out->grad_opacity);
     GS_REQUIRE_DEV(out->grad_scale); GS_REQUIRE_DEV(out->grad_quaternion);
@@ -2756,6 +2800,12 @@ int gsplat_backward_pass_camera(gsplat_context *c, const gsplat_gaussians *g, co
 int gsplat_context_set_depth(gsplat_context *c, int enabled) {
   GS_REQUIRE(c != nullptr, "null context");
   c->depth = enabled != 0;
+  return GSPLAT_OK;
+}
+
+int gsplat_context_set_antialiased(gsplat_context *c, int enabled) {
+  GS_REQUIRE(c != nullptr, "null context");
+  c->antialiased = enabled != 0;  // (read by the next forward; a backward follows the forward it belongs to)
   return GSPLAT_OK;
 }
 

@@ -135,13 +135,25 @@ __device__ __forceinline__ MV mv_from(const float *J, const float *s, const Mat3
 }
 
 // ---- G2b: 2-D covariance -> conic + OBB radii (reference: compute_conic_kernel, cuda/gaussian.cu:77-175)
+// kRho (anti-aliased mode, gsplat_context_set_antialiased): also hands back the entries a, b, c of M Sigma M^T BEFORE the
+// 0.3 blur in cov[3] and the opacity compensation rho = sqrt(max(0, det(cov) / det(cov + 0.3 I))) (a NaN or negative
+// ratio gives 0); conic and radii are what they are without the flag.
+template <bool kRho = false>
 __device__ __forceinline__ void conic_radius(const float *J, const float *s, const Mat34 &vw, float mh_dist,
-                                             float *conic /*3*/, float *radius /*4*/) {
+                                             float *conic /*3*/, float *radius /*4*/, float *rho = nullptr,
+                                             float *cov = nullptr /*3*/) {
   const MV a = mv_from(J, s, vw);
-  const float cov00 = a.m[0] * a.v[0] + a.m[1] * a.v[2] + a.m[2] * a.v[4] + 0.3f;
+  const float raw00 = a.m[0] * a.v[0] + a.m[1] * a.v[2] + a.m[2] * a.v[4];
   const float cov01 = a.m[0] * a.v[1] + a.m[1] * a.v[3] + a.m[2] * a.v[5];
-  const float cov11 = a.m[3] * a.v[1] + a.m[4] * a.v[3] + a.m[5] * a.v[5] + 0.3f;
+  const float raw11 = a.m[3] * a.v[1] + a.m[4] * a.v[3] + a.m[5] * a.v[5];
+  const float cov00 = raw00 + 0.3f;
+  const float cov11 = raw11 + 0.3f;
   const float det = cov00 * cov11 - cov01 * cov01;
+  if constexpr (kRho) {
+    const float det0 = raw00 * raw11 - cov01 * cov01;
+    *rho = sqrtf(fmaxf(0.0f, det0 / det));
+    cov[0] = raw00; cov[1] = cov01; cov[2] = raw11;
+  }
   const float inv_det = 1.0f / det;
   conic[0] = cov11 * inv_det;
   conic[1] = -cov01 * inv_det;
@@ -430,18 +442,54 @@ __device__ __forceinline__ void jacobian_bwd(float x, float y, float z, float fx
   }
 }
 
+// ---- anti-aliased mode: dL/d rho -> dL/d cov2d, the term conic_bwd<.., true> takes.  cov = (a, b, c) before the blur,
+// rho as conic_radius<true> returned them.  With det0 = a c - b^2, det1 = a' c' - b^2 (a' = a + 0.3, c' = c + 0.3) and
+// rho = sqrt(det0 / det1):  d rho/d det0 = 1 / (2 rho det1), d rho/d det1 = -rho / (2 det1), so
+//   d rho/da = (c / rho - rho c') / (2 det1),  d rho/db = -b (1 / rho - rho) / det1,  d rho/dc = (a / rho - rho a') / (2 det1).
+// Those differences cancel for splats much larger than a pixel (rho -> 1: seven digits gone at a = 1e3), so they are
+// formed from c det1 - c' det0 = 0.3 (c c' + b^2) and det1 - det0 = 0.3 (a + c) + 0.09 -- the same numbers:
+//   d rho/da = 0.15 (c c' + b^2) / (rho det1^2),  d rho/dc = 0.15 (a a' + b^2) / (rho det1^2),
+//   d rho/db = -b (0.3 (a + c) + 0.09) / (rho det1^2).
+// g[1] is the share of ONE off-diagonal entry, half of d/db (conic_bwd's convention: a full symmetric matrix).
+// rho == 0 (the clamp, or det0 == 0): no gradient.
+__device__ __forceinline__ void compensation_bwd(const float *cov, float rho, float drho, float *g /*3*/) {
+  g[0] = g[1] = g[2] = 0.0f;
+  if (!(rho > 0.0f)) return;
+  const float a = cov[0], b = cov[1], c = cov[2];
+  const float a1 = a + 0.3f, c1 = c + 0.3f;
+  const float det1 = a1 * c1 - b * b;
+  const float bb = b * b;
+  const float w = drho / (rho * (det1 * det1));
+  g[0] = w * (0.15f * (c * c1 + bb));
+  g[1] = w * (-0.5f * b * (0.3f * (a + c) + 0.09f));
+  g[2] = w * (0.15f * (a * a1 + bb));
+}
+
+// the split of g_eff = dL/d logit(o), o = sigmoid(logit) rho (row slot 3 in anti-aliased mode), into the two leaves:
+// k = g_eff / (1 - o) (0 where 1 - o == 0), dL/d logit = k (1 - sigma), dL/d rho = k / rho (0 where rho == 0)
+__device__ __forceinline__ void effective_opacity_bwd(float g_eff, float sig, float rho, float &g_logit, float &drho) {
+  const float o = sig * rho;
+  const float om = 1.0f - o;
+  const float k = om == 0.0f ? 0.0f : g_eff / om;
+  g_logit = k * (1.0f - sig);
+  drho = rho == 0.0f ? 0.0f : k / rho;
+}
+
 // ---- H2 (reference: conic_backward_kernel, cuda/gaussian_backward.cu:97-248): increments for J_grad[6], sigma_grad[6]
 // kDM: also hands back dL/dM (M = J W, 2x3 row-major) in dM[6] -- what the camera gradient needs (dL/dW = J^T dL/dM)
-template <bool kDM = false>
+// kCov: dcov[3] (compensation_bwd) is added to the covariance gradient the conic's gradient makes, entry by entry
+template <bool kDM = false, bool kCov = false>
 __device__ __forceinline__ void conic_bwd(const float *J, const float *s, const Mat34 &vw, const float *c,
-                                          const float *dc, float *dJ /*6*/, float *dS /*6*/, float *dM = nullptr) {
+                                          const float *dc, float *dJ /*6*/, float *dS /*6*/, float *dM = nullptr,
+                                          const float *dcov = nullptr) {
   const MV a = mv_from(J, s, vw);
   const float *m = a.m, *v = a.v;
   const float t00 = c[0] * dc[0] + c[1] * dc[1], t01 = c[0] * dc[1] + c[1] * dc[2];
   const float t10 = c[1] * dc[0] + c[2] * dc[1], t11 = c[1] * dc[1] + c[2] * dc[2];
-  const float d00 = -(t00 * c[0] + t01 * c[1]);
-  const float d01 = -(t00 * c[1] + t01 * c[2]);
-  const float d11 = -(t10 * c[1] + t11 * c[2]);
+  float d00 = -(t00 * c[0] + t01 * c[1]);
+  float d01 = -(t00 * c[1] + t01 * c[2]);
+  float d11 = -(t10 * c[1] + t11 * c[2]);
+  if constexpr (kCov) { d00 += dcov[0]; d01 += dcov[1]; d11 += dcov[2]; }
   const float dv00 = d00 * m[0] + d01 * m[3], dv01 = d01 * m[0] + d11 * m[3];
   const float dv10 = d00 * m[1] + d01 * m[4], dv11 = d01 * m[1] + d11 * m[4];
   const float dv20 = d00 * m[2] + d01 * m[5], dv21 = d01 * m[2] + d11 * m[5];

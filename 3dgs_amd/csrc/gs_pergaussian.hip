@@ -73,6 +73,25 @@ __global__ __launch_bounds__(kBlock) void conic_kernel(const float *__restrict__
   if (radius) reinterpret_cast<float4 *>(radius)[i] = make_float4(r[0], r[1], r[2], r[3]);
 }
 
+// gsplat_compute_conic_antialiased: conic_kernel plus the opacity compensation rho (gs_math.h: conic_radius<true>)
+__global__ __launch_bounds__(kBlock) void conic_aa_kernel(const float *__restrict__ xyz, const float *__restrict__ view,
+                                                          const float *__restrict__ sigma, float fx, float fy,
+                                                          float tan_fovx, float tan_fovy, float mh_dist, int N,
+                                                          float *__restrict__ J, float *__restrict__ conic,
+                                                          float *__restrict__ radius, float *__restrict__ compensation) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  const gs::Mat34 vw = gs::load_view(view);
+  float j[6], s[6], c[3], r[4], rho, cov[3];
+  gs::jacobian(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], fx, fy, tan_fovx, tan_fovy, j);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { s[k] = sigma[6 * i + k]; J[6 * i + k] = j[k]; }
+  gs::conic_radius<true>(j, s, vw, mh_dist, c, r, &rho, cov);
+  conic[3 * i] = c[0]; conic[3 * i + 1] = c[1]; conic[3 * i + 2] = c[2];
+  reinterpret_cast<float4 *>(radius)[i] = make_float4(r[0], r[1], r[2], r[3]);
+  compensation[i] = rho;
+}
+
 template <int L>
 __global__ __launch_bounds__(kBlock) void sh_forward_kernel(const float *__restrict__ xyz,
                                                             const float *__restrict__ sh,
@@ -142,6 +161,29 @@ __global__ __launch_bounds__(kBlock) void conic_bwd_kernel(const float *__restri
 #pragma unroll
   for (int k = 0; k < 3; ++k) { c[k] = conic[3 * i + k]; dc[k] = gconic[3 * i + k]; }
   gs::conic_bwd(j, s, vw, c, dc, dJ, dS);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { gJ[6 * i + k] += dJ[k]; gsigma[6 * i + k] += dS[k]; }
+}
+
+// gsplat_compute_conic_antialiased_backward: conic_bwd_kernel with the covariance term of dL/d rho; rho and the unblurred
+// covariance are recomputed from J, Sigma and the view (the radii it forms on the way are dead code)
+__global__ __launch_bounds__(kBlock) void conic_aa_bwd_kernel(const float *__restrict__ J, const float *__restrict__ sigma,
+                                                              const float *__restrict__ view,
+                                                              const float *__restrict__ conic,
+                                                              const float *__restrict__ gconic,
+                                                              const float *__restrict__ grho, int N,
+                                                              float *__restrict__ gJ, float *__restrict__ gsigma) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  const gs::Mat34 vw = gs::load_view(view);
+  float j[6], s[6], c[3], dc[3], dJ[6], dS[6], c_unused[3], r_unused[4], rho, cov[3], dcov[3];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { j[k] = J[6 * i + k]; s[k] = sigma[6 * i + k]; }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { c[k] = conic[3 * i + k]; dc[k] = gconic[3 * i + k]; }
+  gs::conic_radius<true>(j, s, vw, 1.0f, c_unused, r_unused, &rho, cov);
+  gs::compensation_bwd(cov, rho, grho[i], dcov);
+  gs::conic_bwd<false, true>(j, s, vw, c, dc, dJ, dS, nullptr, dcov);
 #pragma unroll
   for (int k = 0; k < 6; ++k) { gJ[6 * i + k] += dJ[k]; gsigma[6 * i + k] += dS[k]; }
 }
@@ -477,6 +519,21 @@ int gsplat_compute_conic(const float *xyz, const float *view, const float *sigma
   return GSPLAT_OK;
 }
 
+int gsplat_compute_conic_antialiased(const float *xyz, const float *view, const float *sigma, float focal_x,
+                                     float focal_y, float tan_fovx, float tan_fovy, float mh_dist, int N, float *J,
+                                     float *conic, float *radius, float *compensation, void *stream) {
+  GS_REQUIRE_DEV(xyz); GS_REQUIRE_DEV(sigma); GS_REQUIRE_DEV(view); GS_REQUIRE_DEV(J); GS_REQUIRE_DEV(conic);
+  GS_REQUIRE_DEV(radius); GS_REQUIRE_DEV(compensation);
+  GS_REQUIRE(((uintptr_t)radius & 15) == 0, "radius must be 16-byte aligned (float4)");
+  GS_REQUIRE(N >= 0, "N < 0");
+  if (N == 0) return GSPLAT_OK;
+  conic_aa_kernel<<<gs::div_up(N, kBlock), kBlock, 0, (hipStream_t)stream>>>(xyz, view, sigma, focal_x, focal_y, tan_fovx,
+                                                                            tan_fovy, mh_dist, N, J, conic, radius,
+                                                                            compensation);
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
 int gsplat_precompute_spherical_harmonics(const float *xyz, const float *sh_coefficients,
                                           const float *sh_coeffs_band_0, float campos_x, float campos_y,
                                           float campos_z, int l_max, int N, float *rgb, void *stream) {
@@ -540,6 +597,20 @@ int gsplat_compute_conic_backward(const float *J, const float *sigma, const floa
   if (N == 0) return GSPLAT_OK;
   conic_bwd_kernel<<<gs::div_up(N, kBlock), kBlock, 0, (hipStream_t)stream>>>(J, sigma, view, conic, conic_grad_out, N,
                                                                              J_grad_in, sigma_grad_in);
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int gsplat_compute_conic_antialiased_backward(const float *J, const float *sigma, const float *view, const float *conic,
+                                              const float *conic_grad_out, const float *compensation_grad_out, int N,
+                                              float *J_grad_in, float *sigma_grad_in, void *stream) {
+  GS_REQUIRE_DEV(J); GS_REQUIRE_DEV(sigma); GS_REQUIRE_DEV(view); GS_REQUIRE_DEV(conic);
+  GS_REQUIRE_DEV(conic_grad_out); GS_REQUIRE_DEV(compensation_grad_out); GS_REQUIRE_DEV(J_grad_in);
+  GS_REQUIRE_DEV(sigma_grad_in);
+  GS_REQUIRE(N >= 0, "N < 0");
+  if (N == 0) return GSPLAT_OK;
+  conic_aa_bwd_kernel<<<gs::div_up(N, kBlock), kBlock, 0, (hipStream_t)stream>>>(
+      J, sigma, view, conic, conic_grad_out, compensation_grad_out, N, J_grad_in, sigma_grad_in);
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;
 }

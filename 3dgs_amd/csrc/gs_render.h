@@ -46,16 +46,22 @@ __device__ __forceinline__ float footprint(float a, float b, float c, float opa,
   return tau2;
 }
 
-__device__ __forceinline__ SplatRec make_record(float u, float v, float a, float b, float c, float logit, float r,
-                                                float g, float bl) {
+// make_record on an opacity that is already a probability: the anti-aliased forward hands in sigmoid(logit) * rho
+// (gsplat_context_set_antialiased), and everything the record derives from the opacity follows it
+__device__ __forceinline__ SplatRec make_record_opa(float u, float v, float a, float b, float c, float opa, float r,
+                                                    float g, float bl) {
   SplatRec s;
-  const float opa = sigmoid_fast(logit);
   float hx, hy;
   const float tau2 = footprint(a, b, c, opa, hx, hy);
   s.r0 = make_float4(u, v, a, b);
   s.r1 = make_float4(c, opa, hx, hy);
   s.r2 = make_float4(r, g, bl, tau2);
   return s;
+}
+
+__device__ __forceinline__ SplatRec make_record(float u, float v, float a, float b, float c, float logit, float r,
+                                                float g, float bl) {
+  return make_record_opa(u, v, a, b, c, sigmoid_fast(logit), r, g, bl);
 }
 
 // 16-bit mask: bit (4*by + bx) set when the ellipse alpha >= 1/255 may touch the 4x4 pixel block (bx, by) of the tile

@@ -381,10 +381,13 @@ class ViewShardedStep:
     absgrad=True: the step switches its context to absgrad mode (RasterContext.set_absgrad; False switches it off) and
     the per-view statistic is absnorm, the norm of the absolute sums of the pixels' shares of grad_uv, on every payload:
     `uv_norm_sum` is then the sum of absnorm over the ranks.  The gradients are the same either way.
+
+    antialiased=True: the step switches its context to anti-aliased mode (RasterContext.set_antialiased; False switches
+    it off): the view is rendered with the compensated opacities and every payload carries the gradients of that image.
     """
 
     def __init__(self, params, l_max, width, height, config, bg, exchange="split", with_uv_norm=False, ctx=None,
-                 comm=None, chunks=None, exchange_at_world_one=False, absgrad=False):
+                 comm=None, chunks=None, exchange_at_world_one=False, absgrad=False, antialiased=False):
         from . import raster
         self.raster = raster
         self.params, self.l_max, self.config, self.bg = params, l_max, config, bg
@@ -398,6 +401,8 @@ class ViewShardedStep:
         self.ctx = ctx
         self.absgrad = bool(absgrad)
         ctx.set_absgrad(self.absgrad)
+        self.antialiased = bool(antialiased)
+        ctx.set_antialiased(self.antialiased)
         self.width_cols = wc = raster.packed_gradient_width(l_max)
         self.dev = dev = params["xyz"].device
         self.comm = comm if comm is not None else TorchComm()  # ThreadComm: in-process ranks (ThreadGroup)

@@ -59,6 +59,15 @@ def compute_conic(xyz, view, sigma, focal_x, focal_y, tan_fovx, tan_fovy, mh_dis
                                            N, _p(J), _p(conic), _p(radius), _stream()))
 
 
+def compute_conic_antialiased(xyz, view, sigma, focal_x, focal_y, tan_fovx, tan_fovy, mh_dist, N, J, conic, radius,
+                              compensation):
+    """compute_conic plus compensation[N] = rho, the opacity compensation of anti-aliased mode
+    (gsplat_compute_conic_antialiased)."""
+    check(_lib.load().gsplat_compute_conic_antialiased(_p(xyz), _p(view), _p(sigma), focal_x, focal_y, tan_fovx, tan_fovy,
+                                                       mh_dist, N, _p(J), _p(conic), _p(radius), _p(compensation),
+                                                       _stream()))
+
+
 def get_sorted_gaussian_list(uv, xyz, radius, n_tiles_x, n_tiles_y, N, count, sorted_gaussians, ranges):
     """Two-call protocol.  ``count`` is the in/out size_t of the reference, passed as an int; returns the count
     (call 1: number of candidate pairs; call 2: unchanged)."""
@@ -99,6 +108,15 @@ def compute_projection_jacobian_backward(xyz_c, focal_x, focal_y, tan_fovx, tan_
 def compute_conic_backward(J, sigma, view, conic, conic_grad_out, N, J_grad_in, sigma_grad_in):
     check(_lib.load().gsplat_compute_conic_backward(_p(J), _p(sigma), _p(view), _p(conic), _p(conic_grad_out), N,
                                                     _p(J_grad_in), _p(sigma_grad_in), _stream()))
+
+
+def compute_conic_antialiased_backward(J, sigma, view, conic, conic_grad_out, compensation_grad_out, N, J_grad_in,
+                                       sigma_grad_in):
+    """compute_conic_backward plus the covariance term of compensation_grad_out[N] = dL/d rho; J_grad_in +=,
+    sigma_grad_in += (gsplat_compute_conic_antialiased_backward)."""
+    check(_lib.load().gsplat_compute_conic_antialiased_backward(_p(J), _p(sigma), _p(view), _p(conic), _p(conic_grad_out),
+                                                                _p(compensation_grad_out), N, _p(J_grad_in),
+                                                                _p(sigma_grad_in), _stream()))
 
 
 def compute_sigma_backward(quaternion, scale, sigma_grad_out, N, quaternion_grad_in, scale_grad_in):

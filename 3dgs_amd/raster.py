@@ -178,6 +178,13 @@ class RasterContext:
         gradient is unchanged."""
         check(self._lib.gsplat_context_set_absgrad(self._h, int(bool(enabled))))
 
+    def set_antialiased(self, enabled):
+        """Anti-aliased mode (gsplat_context_set_antialiased): from the next forward on, every gaussian composites with
+        the opacity sigmoid(logit) * rho, rho = sqrt(det(cov) / det(cov + 0.3 I)) -- the compensation for the 0.3 px blur
+        of the projected covariance -- and backward_pass / backward_gaussians (whole, range, split) return the gradients
+        of that image.  The Adam-inside and camera backwards and the two-kernel forward refuse the mode."""
+        check(self._lib.gsplat_context_set_antialiased(self._h, int(bool(enabled))))
+
     def absgrad_uv(self):
         """abs_uv [M,2] of the last compositing backward (compacted order): (sum_p |du_p|, sum_p |dv_p|) over the pixels'
         shares of grad_uv.  Valid until the next forward; an error unless that backward ran in absgrad mode

@@ -30,7 +30,11 @@ DEFAULT_CONFIG = dict(
     delete_opacity_threshold=0.02, uv_grad_threshold=0.0002, split_scale_factor=1.6,
     # absgrad: uv_grad_accum sums, per view, the norm of the ABSOLUTE sums of the pixels' shares of grad_uv instead of
     # |grad_uv| (RasterContext.set_absgrad); uv_grad_threshold is compared as given and has to be raised with it (README)
-    absgrad=False)
+    absgrad=False,
+    # antialiased: every gaussian composites with sigmoid(opacity) * rho, the opacity compensation for the 0.3 px blur of
+    # its projected covariance (RasterContext.set_antialiased), in training and in evaluate(); the optimizer step then
+    # runs behind the backward (the GSPLAT_FUSED_ADAM=0 choreography), which has no Adam-inside form in the mode
+    antialiased=False)
 
 
 def _logit(p):
@@ -77,6 +81,8 @@ class Trainer:
         #   2: all six groups inside the backward (one fat kernel at three waves per SIMD: 356 us, 2 % slower);
         #   0: the backward stores its gradients, the two optimizer kernels read them (r01-r05).
         self.fused_adam = int(__import__("os").environ.get("GSPLAT_FUSED_ADAM", "1") or 0)
+        if self.cfg["antialiased"]:
+            self.fused_adam = 0  # whatever the environment says: the Adam-inside backward refuses the mode
         self._sharded = None  # (key, ViewShardedStep) for the current gaussian count / SH degree
         self._grad_image = {}  # (H, W) -> dL/dimage buffer, allocated once per image size
         self._grads = None     # (capacity, l_max, dict): per-view gradient arrays, reused across iterations
@@ -95,6 +101,7 @@ class Trainer:
         self.ctx = raster.RasterContext(max(n, 1), W, H)
         self.ctx.set_lean_forward(True)  # the loop only runs the fused backward, which recomputes Sigma / J / conic
         self.ctx.set_absgrad(bool(self.cfg["absgrad"]))
+        self.ctx.set_antialiased(bool(self.cfg["antialiased"]))
         self.ctx_capacity = n
         self._new_optimizer(None)
         self.history = []
@@ -122,6 +129,7 @@ class Trainer:
             self.ctx = raster.RasterContext(self.ctx_capacity, W, H)
             self.ctx.set_lean_forward(True)
             self.ctx.set_absgrad(bool(self.cfg["absgrad"]))
+            self.ctx.set_antialiased(bool(self.cfg["antialiased"]))
         return self.ctx
 
     # ------------------------------------------------------------------ one iteration (cuda/trainer.cu:1338-1362)
@@ -171,14 +179,15 @@ class Trainer:
         grad_image = self._grad_image_for(H, W, gt_image.device)
         # the loss value is a blocking read-back: only fetched when the caller logs it
         loss = ops.fused_loss(fwd["image"], gt_image, H, W, float(c["ssim_frac"]), grad_image, blocking=want_loss)
-        if self.fused_adam == 3:
+        fused_adam = 0 if c["antialiased"] else self.fused_adam
+        if fused_adam == 3:
             # r06: the SH group's step in a kernel that reads the coefficient rows once (update + the sums the position
             # gradient needs), then the per-gaussian backward with the five small groups' steps inside: no gradient arrays
             ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it, mode=2))
-        elif self.fused_adam == 2:
+        elif fused_adam == 2:
             # r06: the per-gaussian backward applies the optimizer step itself (no gradient arrays at all)
             ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it))
-        elif self.fused_adam == 1:
+        elif fused_adam == 1:
             g2 = self._partial_gradients_for(ctx, fwd["num_culled"])
             ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it, mode=1), g2)
             self.opt.step_after_partial_backward(it, fwd, g2, cam["campos"])
@@ -206,7 +215,7 @@ class Trainer:
             p = dict(self.params)
             self._sharded = (key, ViewShardedStep(p, self.l_max, ctx.max_width, ctx.max_height, c, 0.0,
                                                   exchange=self.exchange, with_uv_norm=True, ctx=ctx, comm=self.comm,
-                                                  absgrad=bool(c["absgrad"])))
+                                                  absgrad=bool(c["absgrad"]), antialiased=bool(c["antialiased"])))
         step = self._sharded[1]
         H, W = int(cam["height"]), int(cam["width"])
         out = {}
@@ -262,7 +271,8 @@ class Trainer:
         return self.history
 
     def evaluate(self, views=None):
-        """Mean PSNR over the views at background 0 (TrainerImpl::evaluate, cuda/trainer.cu:263-360)."""
+        """Mean PSNR over the views at background 0 (TrainerImpl::evaluate, cuda/trainer.cu:263-360), rendered in the
+        mode the run trains in (config key antialiased)."""
         total, views = 0.0, (views or self.views)
         ctx = self._context_for(self.num_gaussians)
         ctx.set_render_only(True)  # nothing here runs a backward

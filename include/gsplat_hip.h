@@ -679,6 +679,34 @@ int gsplat_context_set_absgrad(gsplat_context *ctx, int enabled);
 int gsplat_context_absgrad_uv(gsplat_context *ctx, float *abs_uv, void *stream);
 int gsplat_pack_absgrad_norm(gsplat_context *ctx, int num_gaussians, float *uv_norm, void *stream);
 
+/* Anti-aliased rasterization: opacity compensation for the 0.3 px blur (Mip-Splatting; gsplat's
+ * rasterize_mode="antialiased").  Every projected covariance gets +0.3 on its diagonal, which dilates a sub-pixel splat
+ * without dimming it.  With a, b, c the entries of M Sigma M^T before the blur, a' = a + 0.3f, c' = c + 0.3f,
+ *   det0 = a c - b^2,   det1 = a' c' - b^2,   rho = sqrtf(fmaxf(0, det0 / det1))      (a NaN or negative ratio gives 0)
+ * and in the mode a gaussian composites with the effective opacity o = sigmoid(logit) * rho.  Conic, radii, culling and
+ * tile lists are unchanged; a gaussian with rho == 0 contributes nothing and receives zero gradient.  The backward: the
+ * compositing backward's opacity gradient is g_eff = dL/d logit(o); the per-gaussian backward forms
+ *   k = g_eff / (1 - o) (0 where 1 - o == 0),   dL/d logit = k (1 - sigma),   dL/d rho = k / rho (0 where rho == 0),
+ * and dL/d rho reaches J, Sigma and the position through d rho/d det0 = 1 / (2 rho det1), d rho/d det1 = -rho / (2 det1),
+ * d det0/d(a, b, c) = (c, -2b, a), d det1/d(a, b, c) = (c', -2b, a').  There is no gradient through the clamp.
+ *   gsplat_context_set_antialiased  a mode of the context (default 0), read by the next gsplat_rasterize_image; a backward
+ *                                   follows the mode its forward ran in.  Lean, full, depth and absgrad contexts alike; rho
+ *                                   is recomputed by the backward, nothing is stored.
+ * With the mode on, GSPLAT_ERR_INVALID_ARG before anything is launched from: gsplat_rasterize_image when the two-kernel
+ * forward is selected (gsplat_context_set_preprocess_split != 0); gsplat_backward_gaussians_adam (it steps the opacity
+ * before the covariance chain exists); gsplat_backward_gaussians_camera / gsplat_backward_pass_camera.
+ * The two operators below are the new arithmetic by itself (one thread per gaussian, gsplat_compute_conic's shape):
+ *   gsplat_compute_conic_antialiased            gsplat_compute_conic plus compensation[N] = rho;
+ *   gsplat_compute_conic_antialiased_backward   gsplat_compute_conic_backward plus compensation_grad[N] = dL/d rho:
+ *                                               J_grad_in +=, sigma_grad_in += of both terms. */
+int gsplat_context_set_antialiased(gsplat_context *ctx, int enabled);
+int gsplat_compute_conic_antialiased(const float *xyz, const float *view, const float *sigma, float focal_x,
+                                     float focal_y, float tan_fovx, float tan_fovy, float mh_dist, int N, float *J,
+                                     float *conic, float *radius, float *compensation, void *stream);
+int gsplat_compute_conic_antialiased_backward(const float *J, const float *sigma, const float *view, const float *conic,
+                                              const float *conic_grad_out, const float *compensation_grad_out, int N,
+                                              float *J_grad_in, float *sigma_grad_in, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
