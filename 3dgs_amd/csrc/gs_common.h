@@ -12,6 +12,7 @@
 #include <cstring>
 
 #include "../../include/gsplat_hip.h"
+#include "gs_forward_plan.h"
 
 namespace gs {
 
@@ -20,19 +21,22 @@ void set_error(const char *fmt, ...);
 // NULL -> GSPLAT_ERR_NULL_POINTER, host/unknown memory -> GSPLAT_ERR_NOT_DEVICE
 int check_device_ptr(const void *p, const char *name, const char *fn);
 
-#define GS_REQUIRE_DEV(p)                                                  \
+// (the _IN forms: checks shared by several entry points report the public function the caller called, passed as `fn`)
+#define GS_REQUIRE_DEV_IN(fn, p)                                           \
   do {                                                                     \
-    int _st = ::gs::check_device_ptr((p), #p, __func__);                   \
+    int _st = ::gs::check_device_ptr((p), #p, fn);                         \
     if (_st != GSPLAT_OK) return _st;                                      \
   } while (0)
+#define GS_REQUIRE_DEV(p) GS_REQUIRE_DEV_IN(__func__, p)
 
-#define GS_REQUIRE(cond, msg)                                              \
+#define GS_REQUIRE_IN(fn, cond, msg)                                       \
   do {                                                                     \
     if (!(cond)) {                                                         \
-      ::gs::set_error("%s: invalid argument: %s", __func__, msg);          \
+      ::gs::set_error("%s: invalid argument: %s", fn, msg);                \
       return GSPLAT_ERR_INVALID_ARG;                                       \
     }                                                                      \
   } while (0)
+#define GS_REQUIRE(cond, msg) GS_REQUIRE_IN(__func__, cond, msg)
 
 #define GS_HIP(call)                                                                          \
   do {                                                                                        \
@@ -69,15 +73,7 @@ __host__ __device__ inline int bin_slice_first_chunk(int C, int s) { return (int
 __host__ __device__ inline int bin_slice_of_chunk(int C, int c) {
   return (int)((((long long)c + 1) * kBinBlocks - 1) / C);
 }
-// The forward's host record: pinned, mapped host memory the GPU writes and the host polls.  Five 64-bit words, each
-// {value << 32 | low half of the forward's ticket}: M, S, candidate pairs (low, high), longest tile list.  A word is
-// one aligned 8-byte store, so it cannot tear, and the host takes the record when all five carry its ticket -- no
-// ordering between the stores is needed, hence no __threadfence_system() (a system-scope release writes back the
-// XCD's whole L2: several microseconds on the GPU's critical path, behind kernels that left megabytes dirty).
-constexpr int kRecordWords = 5;
-__host__ __device__ inline unsigned long long record_word(unsigned int value, unsigned long long ticket) {
-  return ((unsigned long long)value << 32) | (ticket & 0xFFFFFFFFull);
-}
+// The forward's host record (gs_forward_plan.h: kRecordWords, record_word), as the device writes it
 #ifdef __HIPCC__
 __device__ inline void publish_record(volatile unsigned long long *pub, unsigned long long ticket, unsigned int M,
                                       unsigned int S, unsigned long long pairs, unsigned int longest) {

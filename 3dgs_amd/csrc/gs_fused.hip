@@ -2,10 +2,10 @@
 // rasterize_image, cuda/raster.cu:12-136) and gsplat_backward_pass (the operator chain of
 // TrainerImpl::backward_pass, cuda/trainer.cu:941-1012) on a persistent workspace.
 //
-// Forward:   project+cull (N)  ->  scan(mask)  ->  preprocess (fused SH / Sigma / J / conic /
-//            radius / splat record / exact tile count, written in compacted order)
-//            ->  scan(counts)  ->  ONE host read-back {M, S}  ->  emit keys  ->  radix sort
-//            ->  tile ranges  ->  compositing.
+// Forward:   project_cull -> preprocess<L> -> bin_offsets -> bin_scatter -> tile_depth_sort_* -> render_fwd (the
+//            sparse route; dense scenes and very large tile grids take radix sorts).  ONE host read-back, the record
+//            bin_scatter publishes: everything behind the counts is queued BEFORE the host waits for it, bounded by
+//            instance_room(), and queued again if the record shows that it did not fit (decisions: gs_forward_plan.h).
 // Backward:  zero gradient rows -> compositing backward (64-byte row atomics) -> one fused
 //            per-gaussian kernel for the whole SH / conic / Jacobian / Sigma / projection chain.
 // The reference runs ~20 thrust compactions, ~15 kernels and 5 blocking read-backs for the
@@ -14,7 +14,6 @@
 #include <cmath>
 #include <new>
 #include <rocprim/rocprim.hpp>
-
 #include <cstdlib>
 
 #include "gs_common.h"
@@ -119,8 +118,8 @@ struct gsplat_context {
   double fseg_gate = -1.0;  // < 0: GSPLAT_FWD_SEGMENTS_GATE / its default
   unsigned long long n_segmented_forwards = 0;
   // r06: the figures the segment kernels publish, as the host last took them from a slot whose ticket it could trust
-  // (queue_tail): the largest stop index of any tile, the sum over the tiles, the segments / segment blocks asked for
-  long long fig_max = 0, fig_sum = 0, fig_asked_bwd = 0, fig_asked_fwd = 0;
+  // (gs::take_figures)
+  gs::Figures fig;
   int seg_cap = 0;          // extra segments the recorded forward had room for
   bool seg_ready = false;   // the recorded forward wrote the table and the checkpoints
   unsigned long long n_segmented_backwards = 0;
@@ -1962,7 +1961,7 @@ int gsplat_context_create(gsplat_context **out, int max_gaussians, int max_width
       gs::set_error("gsplat_context_create: could not map the count record");
       rc = GSPLAT_ERR_HIP;
     } else {
-      memset(h, 0, 256);  // words 0..4: the forward's record; 8..15: two slots of four tagged figures (queue_tail)
+      memset(h, 0, 256);  // words 0..4: the forward's record; 8..15: two slots of four tagged figures (queue_sparse_tail)
       c->h_pub = (volatile unsigned long long *)h;
       c->d_pub = (unsigned long long *)d;
     }
@@ -1990,72 +1989,80 @@ int gsplat_context_destroy(gsplat_context *ctx) {
 
 size_t gsplat_context_bytes(const gsplat_context *ctx) { return ctx ? ctx->bytes() : 0; }
 
-int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
-                           const gsplat_raster_config *cfg, float bg_color, int l_max, gsplat_forward_view *out,
-                           void *stream) {
-  GS_REQUIRE(c && g && cam && cfg, "null argument struct");
-  GS_REQUIRE(l_max >= 0 && l_max <= 3, "l_max must be 0..3");  // cuda/raster.cu:58-60
+// ---- gsplat_rasterize_image: the forward as a sequence of steps.  What the steps share is gathered once per call in
+// FwdCall; every decision they take is a function of gs_forward_plan.h.
+struct FwdCall {
+  const gsplat_gaussians *g; const gsplat_camera *cam; const gsplat_raster_config *cfg;  // the caller's, with bg, l_max, st
+  float bg; hipStream_t st;
+  int l_max, N, W, H, ntx, nty, num_tiles;
+  float tan_fovx, tan_fovy;  // cuda/raster.cu:92-93
+  bool compact;              // the per-gaussian kernels walk the compacted slots (gs::compact_walk)
+  bool beside;               // the colour kernel beside the geometry kernel (pre_split 2)
+  bool ro, mid;              // render only; Sigma, J, conic, colour stored for the caller / the stand-alone backward operators
+  bool sparse, keys_ok;      // the counting-sort route (else the radix sorts); every depth key an ordinary positive float
+  int *bin_table; size_t hist_bytes;  // sparse route: the per-workgroup tile histograms, and the LDS one takes
+  unsigned long long ticket;  // of the host record and the figure slots
+  gs::DepthMaps dmap;         // depth mode: the compositing kernels' depth instantiations (gs_render.h: DepthMaps)
+  bool join_pending;          // pre_split 2 with the late join: the colour kernel is waited for in front of render_fwd
+  bool segmented_this_forward;
+};
+static int check_forward_args(const gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                              const gsplat_raster_config *cfg, int l_max) {
+  static const char fn[] = "gsplat_rasterize_image";
+  GS_REQUIRE_IN(fn, c && g && cam && cfg, "null argument struct");
+  GS_REQUIRE_IN(fn, l_max >= 0 && l_max <= 3, "l_max must be 0..3");  // cuda/raster.cu:58-60
   const int N = g->num_gaussians, W = cam->width, H = cam->height;
-  GS_REQUIRE(N > 0, "num_gaussians must be positive");
+  GS_REQUIRE_IN(fn, N > 0, "num_gaussians must be positive");
   if (N > c->max_gaussians || W > c->max_width || H > c->max_height || W <= 0 || H <= 0) {
     gs::set_error("gsplat_rasterize_image: %d gaussians / %dx%d exceed the context capacity %d / %dx%d", N, W, H,
                   c->max_gaussians, c->max_width, c->max_height);
     return GSPLAT_ERR_CAPACITY;
   }
-  GS_REQUIRE_DEV(g->xyz); GS_REQUIRE_DEV(g->rgb); GS_REQUIRE_DEV(g->opacity); GS_REQUIRE_DEV(g->scale);
-  GS_REQUIRE_DEV(g->quaternion); GS_REQUIRE_DEV(cam->view); GS_REQUIRE_DEV(cam->proj);
-  if (l_max > 0) GS_REQUIRE_DEV(g->sh);
-  GS_REQUIRE(((uintptr_t)g->quaternion & 15) == 0, "quaternion must be 16-byte aligned");
-  GS_REQUIRE(!(c->antialiased && c->pre_split),
-             "anti-aliased mode has no two-kernel forward (gsplat_context_set_preprocess_split / GSPLAT_PRE_SPLIT must be 0)");
-  hipStream_t st = (hipStream_t)stream;
-  c->have_forward = false;
-  c->rows_ready = false;
-  c->order_ready = false;
-  c->depth_ready = false;
-  c->rows_depth = false;
-  c->rows_abs = false;
+  GS_REQUIRE_DEV_IN(fn, g->xyz); GS_REQUIRE_DEV_IN(fn, g->rgb); GS_REQUIRE_DEV_IN(fn, g->opacity); GS_REQUIRE_DEV_IN(fn, g->scale);
+  GS_REQUIRE_DEV_IN(fn, g->quaternion); GS_REQUIRE_DEV_IN(fn, cam->view); GS_REQUIRE_DEV_IN(fn, cam->proj);
+  if (l_max > 0) GS_REQUIRE_DEV_IN(fn, g->sh);
+  GS_REQUIRE_IN(fn, ((uintptr_t)g->quaternion & 15) == 0, "quaternion must be 16-byte aligned");
+  GS_REQUIRE_IN(fn, !(c->antialiased && c->pre_split),
+                "anti-aliased mode has no two-kernel forward (gsplat_context_set_preprocess_split / GSPLAT_PRE_SPLIT must be 0)");
+  GS_REQUIRE_IN(fn, N <= (64 << 20), "more than 64 Mi gaussians: the cull's per-slice ballots would not fit its LDS");
+  return GSPLAT_OK;
+}
+
+// The recorded forward is void from here on; outputs the caller took over (gsplat_context_detach_forward_outputs) come
+// back from the pool, at their old sizes
+static int reclaim_outputs(gsplat_context *c, hipStream_t st) {
+  c->have_forward = c->rows_ready = c->order_ready = c->depth_ready = c->rows_depth = c->rows_abs = false;
   gs::pool_unwatch(&c->last_mask);
   c->last_mask = nullptr;  // rank[] and compact_to_global are about to be overwritten
-  {  // outputs the caller took over (gsplat_context_detach_forward_outputs) come back from the pool, at their old sizes
-    gs::DeviceBuffer *outs[13];
-    c->forward_outputs(outs);
-    for (gs::DeviceBuffer *b : outs)
-      if (b->ptr == nullptr) {
-        const int r = b->reserve_again(st);  // (ordered behind the stream that returned the block, if another)
-        if (r) return r;
-        // a fresh `sorted` must hold valid gaussian ids wherever the speculative tail may read it (reserve_instances)
-        if (b == &c->sorted) GS_HIP(hipMemsetAsync(b->ptr, 0, b->bytes, st));
-      }
-  }
-  const int ntx = (W + 15) / 16, nty = (H + 15) / 16, num_tiles = ntx * nty;
-  const float fx = cam->focal_x, fy = cam->focal_y;
-  const float tan_fovx = (float)W / (2.0f * fx), tan_fovy = (float)H / (2.0f * fy);  // cuda/raster.cu:92-93
-  // depth mode: the compositing kernels' depth instantiations (gs_render.h: DepthMaps); z from the compacted xyz_c, which
-  // preprocess writes in every mode
-  gs::DepthMaps dmap = {};
-  if (c->depth) {
-    const int r = c->depth_map.reserve((size_t)W * H * sizeof(float), st);
-    if (r) return r;
-    dmap.xyz_c = c->xyz_c.as<float>();
-    dmap.depth = c->depth_map.as<float>();
-  }
+  gs::DeviceBuffer *outs[13];
+  c->forward_outputs(outs);
+  for (gs::DeviceBuffer *b : outs)
+    if (b->ptr == nullptr) {
+      const int r = b->reserve_again(st);  // (ordered behind the stream that returned the block, if another)
+      if (r) return r;
+      // a fresh `sorted` must hold valid gaussian ids wherever the speculative tail may read it (reserve_instances)
+      if (b == &c->sorted) GS_HIP(hipMemsetAsync(b->ptr, 0, b->bytes, st));
+    }
+  return GSPLAT_OK;
+}
 
-  if (c->timing) {  // next timing slot; its events are >= kSlots forwards old, hence complete
-    c->slot = (int)(c->fwd_calls % gsplat_context::kSlots);
-    c->harvest(c->slot);
-  }
-  c->fwd_calls++;
-  GS_REQUIRE(N <= (64 << 20), "more than 64 Mi gaussians: the cull's per-slice ballots would not fit its LDS");
-  c->mark(0, false, st);
-  // A view that culled a fifth of the scene or more last time gets the compacted walk in preprocess_kernel (the previous
-  // forward of this context decides: views of a training run look alike; the first call walks all indices).
-  const bool compact = c->N == N && c->M > 0 && (long long)c->M * 5 < (long long)N * 4;
+// Everything the call decides before its first launch, and the buffers / side stream those decisions need
+static int plan_forward_call(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                             const gsplat_raster_config *cfg, float bg_color, int l_max, hipStream_t st, FwdCall &f) {
   int rc = GSPLAT_OK;
-  if (compact && (rc = c->kept.reserve((size_t)c->max_gaussians * sizeof(int)))) return rc;
+  f = {}; f.g = g; f.cam = cam; f.cfg = cfg; f.bg = bg_color; f.l_max = l_max; f.st = st;
+  f.N = g->num_gaussians; f.W = cam->width; f.H = cam->height;
+  f.ntx = (f.W + 15) / 16; f.nty = (f.H + 15) / 16; f.num_tiles = f.ntx * f.nty;
+  f.tan_fovx = (float)f.W / (2.0f * cam->focal_x); f.tan_fovy = (float)f.H / (2.0f * cam->focal_y);
+  if (c->depth) {  // z from the compacted xyz_c, which preprocess writes in every mode
+    if ((rc = c->depth_map.reserve((size_t)f.W * f.H * sizeof(float), st))) return rc;
+    f.dmap.xyz_c = c->xyz_c.as<float>(); f.dmap.depth = c->depth_map.as<float>();
+  }
+  f.compact = gs::compact_walk(c->N, c->M, f.N);
+  if (f.compact && (rc = c->kept.reserve((size_t)c->max_gaussians * sizeof(int)))) return rc;
   // the colour kernel beside the geometry kernel (pre_split 2): its stream and the two events, made on first use
-  const bool beside = c->pre_split == 2 && l_max > 0;
-  if (beside) {
+  f.beside = c->pre_split == 2 && l_max > 0;
+  if (f.beside) {
     if ((rc = c->chunk_first.reserve(((size_t)gs::bin_chunks(c->max_gaussians) + gs::kBinThreads / 64 + 1) * sizeof(int)))) return rc;
     if (!c->pre_side) {
       int lo_prio = 0, hi_prio = 0;
@@ -2065,36 +2072,77 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
       GS_HIP(hipEventCreateWithFlags(&c->ev_pre_join, hipEventDisableTiming));
     }
   }
-  {
-    // LDS of the cull: one ballot + one count per (trip, wave) of the largest slice (a run of whole 64-entry chunks)
-    const size_t slice_max = ((size_t)gs::bin_chunks(N) / gs::kBinBlocks + 2) * gs::kBinChunk;
-    const size_t trips = (slice_max + gs::kBinThreads - 1) / gs::kBinThreads + 1;
-    project_cull_kernel<<<gs::kBinBlocks, gs::kBinThreads, trips * (gs::kBinThreads / 64) * 12, st>>>(
-        g->xyz, cam->view, cam->proj, N, W, H, cfg->near_thresh, cfg->cull_mask_padding,
-        c->lean ? nullptr : c->xyz_c_all.as<float>(), c->lean ? nullptr : c->uv_all.as<float>(),
-        c->mask.as<unsigned char>(), c->rank.as<int>(), c->slice_counts(), c->pair_counters(),
-        compact ? c->kept.as<int>() : nullptr, beside && !compact ? c->chunk_first.as<int>() : nullptr);
-    GS_LAUNCH_CHECK();
-  }
-  c->mark(0, true, st);
-  c->mark(1, false, st);
-  const bool ro = c->render_only;
-  const bool mid = !ro && !c->lean;  // Sigma, J, conic, colour: stored for the caller / the stand-alone backward operators
-  PreOut po = {c->c2g.as<int>(), c->xyz_c.as<float>(), c->uv.as<float>(), mid ? c->sigma.as<float>() : nullptr,
-               mid ? c->conic.as<float>() : nullptr, mid ? c->J.as<float>() : nullptr, mid ? c->rgb.as<float>() : nullptr,
-               c->radius.as<float>(), c->recs.as<float4>(), c->counts.as<int>(),
-               c->hitmask.as<unsigned long long>(), c->pair_counters()};
+  f.ro = c->render_only; f.mid = !f.ro && !c->lean;
   // Two binning routes, both exact for any scene; the choice only affects speed, so it follows the LAST forward's
   // density (the first call starts sparse): sparse = LDS counting sort + per-tile depth sort, dense (more than
   // ~768 list entries per tile) or very large tile grids = stable radix sorts (gs_binning.hip).
   const bool want_dense = c->forced_route == 2 || (c->forced_route == 0 && c->dense_route);
-  const bool sparse = !want_dense && gs::binning_supports_counting_sort(num_tiles);
-  int *bin_table = nullptr;
-  if (sparse) {
-    if ((rc = c->bin_table.reserve(gs::binning_table_bytes(num_tiles)))) return rc;
-    bin_table = c->bin_table.as<int>();
+  f.sparse = !want_dense && gs::binning_supports_counting_sort(f.num_tiles);
+  if (f.sparse) {
+    if ((rc = c->bin_table.reserve(gs::binning_table_bytes(f.num_tiles)))) return rc;
+    f.bin_table = c->bin_table.as<int>();
   }
-  const size_t hist_bytes = sparse ? (size_t)num_tiles * sizeof(int) : 0;
+  f.hist_bytes = f.sparse ? (size_t)f.num_tiles * sizeof(int) : 0;
+  f.keys_ok = cfg->near_thresh >= 1e-30f; f.ticket = ++c->ticket;
+  return GSPLAT_OK;
+}
+
+static int launch_cull(gsplat_context *c, const FwdCall &f) {
+  c->mark(0, false, f.st);
+  // LDS of the cull: one ballot + one count per (trip, wave) of the largest slice (a run of whole 64-entry chunks)
+  const size_t slice_max = ((size_t)gs::bin_chunks(f.N) / gs::kBinBlocks + 2) * gs::kBinChunk;
+  const size_t trips = (slice_max + gs::kBinThreads - 1) / gs::kBinThreads + 1;
+  project_cull_kernel<<<gs::kBinBlocks, gs::kBinThreads, trips * (gs::kBinThreads / 64) * 12, f.st>>>(
+      f.g->xyz, f.cam->view, f.cam->proj, f.N, f.W, f.H, f.cfg->near_thresh, f.cfg->cull_mask_padding,
+      c->lean ? nullptr : c->xyz_c_all.as<float>(), c->lean ? nullptr : c->uv_all.as<float>(),
+      c->mask.as<unsigned char>(), c->rank.as<int>(), c->slice_counts(), c->pair_counters(),
+      f.compact ? c->kept.as<int>() : nullptr, f.beside && !f.compact ? c->chunk_first.as<int>() : nullptr);
+  GS_LAUNCH_CHECK();
+  c->mark(0, true, f.st);
+  return GSPLAT_OK;
+}
+
+// the colour kernel of the two-kernel forms (see sh_colour_kernel), on stream `cst`
+static int launch_colour(gsplat_context *c, const FwdCall &f, hipStream_t cst) {
+  if (f.l_max == 0) return GSPLAT_OK;
+  const gsplat_gaussians *g = f.g; const gsplat_camera *cam = f.cam;
+  const dim3 cg(gs::div_up(gs::bin_chunks(f.N), kBlock / 64)), cb(kBlock);
+  const int *rk = f.beside ? nullptr : c->rank.as<int>();
+  float *rgb_to = f.beside ? (f.mid ? c->rgb.as<float>() : nullptr) : c->rgb.as<float>();
+  float4 *rec_to = f.beside ? c->recs.as<float4>() : nullptr;
+#define GS_SHC(LL)                                                                                                     \
+  do {                                                                                                                 \
+    if (f.compact)                                                                                                     \
+      sh_colour_kernel<LL, true><<<cg, cb, 0, cst>>>(*g, c->mask.as<unsigned char>(), rk, nullptr, c->slice_counts(),   \
+                                                     c->kept.as<int>(), cam->campos[0], cam->campos[1], cam->campos[2], rgb_to, rec_to); \
+    else                                                                                                               \
+      sh_colour_kernel<LL, false><<<cg, cb, 0, cst>>>(*g, c->mask.as<unsigned char>(), rk, c->chunk_first.as<int>(),    \
+                                                      c->slice_counts(), nullptr, cam->campos[0], cam->campos[1], cam->campos[2], rgb_to, rec_to); \
+  } while (0)
+  switch (f.l_max) {
+    case 1: GS_SHC(1); break;
+    case 2: GS_SHC(2); break;
+    default: GS_SHC(3); break;
+  }
+#undef GS_SHC
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+// Everything per kept gaussian: the fused kernel, or the two split forms (r06: colour and geometry as two kernels, one
+// behind the other or side by side; see sh_colour_kernel)
+static int launch_per_gaussian(gsplat_context *c, FwdCall &f) {
+  const gsplat_gaussians *g = f.g; const gsplat_camera *cam = f.cam; const gsplat_raster_config *cfg = f.cfg;
+  const int W = f.W, H = f.H, ntx = f.ntx, nty = f.nty, l_max = f.l_max;  // (the launch macros below name these)
+  const float fx = cam->focal_x, fy = cam->focal_y, tan_fovx = f.tan_fovx, tan_fovy = f.tan_fovy;
+  const bool mid = f.mid, compact = f.compact, beside = f.beside;
+  int *const bin_table = f.bin_table; const size_t hist_bytes = f.hist_bytes; hipStream_t st = f.st;
+  int rc = GSPLAT_OK;
+  c->mark(1, false, st);
+  PreOut po = {c->c2g.as<int>(), c->xyz_c.as<float>(), c->uv.as<float>(), mid ? c->sigma.as<float>() : nullptr,
+               mid ? c->conic.as<float>() : nullptr, mid ? c->J.as<float>() : nullptr, mid ? c->rgb.as<float>() : nullptr,
+               c->radius.as<float>(), c->recs.as<float4>(), c->counts.as<int>(),
+               c->hitmask.as<unsigned long long>(), c->pair_counters()};
 #define GS_PRE3(LL, MID, CMP)                                                                                          \
   if (c->antialiased) GS_PRE4(LL, MID, CMP, true); else GS_PRE4(LL, MID, CMP, false)
 #define GS_PRE4(LL, MID, CMP, AA)                                                                                      \
@@ -2106,9 +2154,7 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
     if (mid) { if (compact) { GS_PRE3(LL, true, true); } else { GS_PRE3(LL, true, false); } }                          \
     else { if (compact) { GS_PRE3(LL, false, true); } else { GS_PRE3(LL, false, false); } }                            \
   } while (0)
-  bool join_pending = false;
   if (c->pre_split) {
-    // r06: colour and geometry as two kernels (see sh_colour_kernel)
     const bool seq = l_max > 0 && c->pre_split == 1;  // one behind the other: the colour travels through c->rgb
     if (seq) po.rgb = c->rgb.as<float>();
     hipStream_t cst = st;
@@ -2117,31 +2163,7 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
       GS_HIP(hipStreamWaitEvent(c->pre_side, c->ev_pre_fork, 0));
       cst = c->pre_side;
     }
-    auto launch_colour = [&]() -> int {
-      if (l_max == 0) return GSPLAT_OK;
-      const dim3 cg(gs::div_up(gs::bin_chunks(N), kBlock / 64)), cb(kBlock);
-      const int *rk = beside ? nullptr : c->rank.as<int>();
-      float *rgb_to = beside ? (mid ? c->rgb.as<float>() : nullptr) : c->rgb.as<float>();
-      float4 *rec_to = beside ? c->recs.as<float4>() : nullptr;
-#define GS_SHC(LL)                                                                                                     \
-  do {                                                                                                                 \
-    if (compact)                                                                                                       \
-      sh_colour_kernel<LL, true><<<cg, cb, 0, cst>>>(*g, c->mask.as<unsigned char>(), rk, nullptr, c->slice_counts(),   \
-                                                     c->kept.as<int>(), cam->campos[0], cam->campos[1], cam->campos[2], rgb_to, rec_to); \
-    else                                                                                                               \
-      sh_colour_kernel<LL, false><<<cg, cb, 0, cst>>>(*g, c->mask.as<unsigned char>(), rk, c->chunk_first.as<int>(),    \
-                                                      c->slice_counts(), nullptr, cam->campos[0], cam->campos[1], cam->campos[2], rgb_to, rec_to); \
-  } while (0)
-      switch (l_max) {
-        case 1: GS_SHC(1); break;
-        case 2: GS_SHC(2); break;
-        default: GS_SHC(3); break;
-      }
-#undef GS_SHC
-      GS_LAUNCH_CHECK();
-      return GSPLAT_OK;
-    };
-    if (seq && (rc = launch_colour())) return rc;
+    if (seq && (rc = launch_colour(c, f, cst))) return rc;
 #define GS_GEOM3(COL, MID, CMP)                                                                                        \
   preprocess_geom_kernel<COL, MID, CMP><<<gs::kBinBlocks, gs::kBinThreads, hist_bytes, st>>>(                          \
       *g, cam->view, c->mask.as<unsigned char>(), c->rank.as<int>(), c->slice_counts(), c->kept.as<int>(),              \
@@ -2157,305 +2179,285 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
 #undef GS_GEOM3
     GS_LAUNCH_CHECK();
     if (beside) {
-      if ((rc = launch_colour())) return rc;
+      if ((rc = launch_colour(c, f, cst))) return rc;
       GS_HIP(hipEventRecord(c->ev_pre_join, c->pre_side));
-      if (gs_pre_join_late()) join_pending = true;
+      if (gs_pre_join_late()) f.join_pending = true;
       else GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));
     }
   } else {
-  switch (l_max) {
-    case 0: GS_PRE(0); break;
-    case 1: GS_PRE(1); break;
-    case 2: GS_PRE(2); break;
-    default: GS_PRE(3); break;
-  }
+    switch (l_max) {
+      case 0: GS_PRE(0); break;
+      case 1: GS_PRE(1); break;
+      case 2: GS_PRE(2); break;
+      default: GS_PRE(3); break;
+    }
   }
 #undef GS_PRE
 #undef GS_PRE3
 #undef GS_PRE4
   GS_LAUNCH_CHECK();
   c->fwd_antialiased = c->antialiased;
-  size_t inst_cap = 0;
-  // the one host read-back of the forward: M, S (and the candidate count)
-  const unsigned long long ticket = ++c->ticket;
-  size_t spec_cap = 0;  // sparse route: room of the instance buffers, what the kernels queued before the wait may use
-  if (sparse) {
-    if (instance_room(c) < 2 && (rc = reserve_instances(c, 4 * (size_t)N, num_tiles, st))) return rc;
-    spec_cap = instance_room(c) - 1;
+  return GSPLAT_OK;
+}
+
+// Counts -> offsets for either route, and on the radix route the record and the emit.  Nothing here needs the totals on
+// the host, only room for its writes: `room` is what the kernels queued before the wait may use of ALL the instance
+// buffers (instance_room), and the host sleeps on the read-back while they run (the reference blocks five times, GPU idle).
+static int queue_counts(gsplat_context *c, const FwdCall &f, size_t &room) {
+  const int N = f.N; hipStream_t st = f.st;
+  int rc = GSPLAT_OK;
+  if (f.sparse) {
+    if (instance_room(c) < 2 && (rc = reserve_instances(c, 4 * (size_t)N, f.num_tiles, st))) return rc;
+    room = instance_room(c) - 1;
     c->mark(1, true, st);
     c->mark(2, false, st);
-    rc = gs::binning_offsets(ntx, nty, bin_table, c->keys_a.as<int>(), st);
-    if (rc) return rc;
-  } else {
-    rc = gs::scan_counts(N, c->counts.as<int>(), c->offsets.as<int>(), c->temp.ptr, c->temp.bytes, st);
-    if (rc) return rc;
-    c->mark(1, true, st);
-    publish_counts_kernel<<<1, 64, 0, st>>>(c->rank.as<int>() + N, c->offsets.as<int>() + N, c->pair_counters(), c->d_pub,
-                                           ticket);
-    GS_LAUNCH_CHECK();
+    return gs::binning_offsets(f.ntx, f.nty, f.bin_table, c->keys_a.as<int>(), st);
   }
-  if (!sparse) {
-    // Emit does not need the totals on the host, only room for its writes: launch it bounded by the buffers'
-    // capacity and sleep on the read-back while it runs (the reference blocks five times per forward, GPU idle).
-    // (the bound is the room of ALL instance arrays: see instance_room)
-    if (instance_room(c) < 2 && (rc = reserve_instances(c, 4 * (size_t)N, num_tiles, st))) return rc;
-    inst_cap = instance_room(c) - 1;
-    c->mark(2, false, st);
-    rc = gs::launch_tile_emit(c->uv.as<float>(), c->xyz_c.as<float>(), c->radius.as<float>(), ntx, nty, N,
+  rc = gs::scan_counts(N, c->counts.as<int>(), c->offsets.as<int>(), c->temp.ptr, c->temp.bytes, st);
+  if (rc) return rc;
+  c->mark(1, true, st);
+  publish_counts_kernel<<<1, 64, 0, st>>>(c->rank.as<int>() + N, c->offsets.as<int>() + N, c->pair_counters(), c->d_pub,
+                                         f.ticket);
+  GS_LAUNCH_CHECK();
+  if (instance_room(c) < 2 && (rc = reserve_instances(c, 4 * (size_t)N, f.num_tiles, st))) return rc;
+  room = instance_room(c) - 1;
+  c->mark(2, false, st);
+  return gs::launch_tile_emit(c->uv.as<float>(), c->xyz_c.as<float>(), c->radius.as<float>(), f.ntx, f.nty, N,
                               c->mask.as<unsigned char>(), c->rank.as<int>(), c->offsets.as<int>(),
-                              c->hitmask.as<unsigned long long>(), (long long)inst_cap,
-                              c->keys_a.as<unsigned int>(), c->pay_a.as<unsigned long long>(), st);
-    if (rc) return rc;
+                              c->hitmask.as<unsigned long long>(), (long long)room, c->keys_a.as<unsigned int>(),
+                              c->pay_a.as<unsigned long long>(), st);
+}
+
+// Sparse route: placement, per-tile sorts and render_fwd, queued before the host knows S (gs::tail_needs_redo has the
+// protocol) and bounded by `cap`: `ranges` on the device are clamped to it (bin_scatter_kernel), so whatever S turns out
+// to be, the kernels stay inside the buffers.  Which long-list kernels to queue follows `longest_hint`; a forward whose
+// tail has to be redone comes through here again, with the true S and longest list.  `publish`: the placement
+// publishes the record.
+static int queue_sparse_tail(gsplat_context *c, FwdCall &f, size_t cap, long long longest_hint, bool publish) {
+  const int num_tiles = f.num_tiles; const bool ro = f.ro; hipStream_t st = f.st;
+  if (cap + 1 > instance_room(c)) {  // every kernel below indexes the instance arrays up to `cap` (inclusive: the spare slot)
+    gs::set_error("gsplat_rasterize_image: internal: %zu instances queued into room for %zu", cap, instance_room(c));
+    return GSPLAT_ERR_CAPACITY;
   }
-  // Sparse route: nothing behind the counts needs them on the HOST -- the placement only needs room for its writes,
-  // the per-tile sorts read `ranges` on the device, the compositing nothing at all.  So scatter, sorts and render_fwd
-  // are queued right here, bounded by the buffers' capacity, and the host sleeps on the read-back while they run (r01
-  // launched them after the wake-up: the GPU idled for the round trip, ~13 us per forward).  Which long-list kernels
-  // to queue follows the previous forward's longest list; afterwards the record is checked, and a forward whose
-  // instances outgrew the buffers or whose longest list needed a kernel that was not queued is redone from the
-  // placement on (results are unaffected: every launch overwrites).
-  // (r06: class 0 -- no list beyond the wave kernel's 1024 entries and every depth key an ordinary positive float: the
-  // hand-over kernel is not queued at all, gs_binning.hip sort_tiles_by_depth)
-  const bool keys_ok = cfg->near_thresh >= 1e-30f;
-  auto list_class = [keys_ok](long long longest) {  // which of the workgroup sort kernels a list of that length needs
-    return longest > 8 * 1024 ? 4 : longest > 4 * 1024 ? 3 : longest > 2 * 1024 ? 2 : (longest > 1024 || !keys_ok) ? 1 : 0;
-  };
-  bool segmented_this_forward = false;
-  auto queue_tail = [&](size_t cap, long long longest_hint, bool publish) -> int {  // the placement publishes the record
-    if (cap + 1 > instance_room(c)) {  // every kernel below indexes the instance arrays up to `cap` (inclusive: the spare slot)
-      gs::set_error("gsplat_rasterize_image: internal: %zu instances queued into room for %zu", cap, instance_room(c));
-      return GSPLAT_ERR_CAPACITY;
-    }
-    if ((longest_hint < 0 || longest_hint > 2048) && !c->fork.ready) {  // lists beyond two register-sorted runs: see SortFork
-      const int fr = c->fork.create();
-      if (fr) return fr;
-    }
-    int r = gs::binning_scatter_and_sort(c->uv.as<float>(), c->xyz_c.as<float>(), c->radius.as<float>(),
-                                         c->hitmask.as<unsigned long long>(), c->rank.as<int>(), N, ntx, nty,
-                                         c->bin_table.as<int>(), c->ranges.as<int>(), cap, c->pay_a.as<unsigned long long>(),
-                                         c->keys_a.as<int>(), c->sorted.as<int>(), longest_hint, c->rank.as<int>() + N,
-                                         c->pair_counters(), publish ? c->d_pub : nullptr, ticket, st, &c->fork, compact,
-                                         keys_ok);
-    if (r) return r;
-    c->mark(2, true, st);
-    c->mark(4, false, st);
-    // Heaviest-first for the backward only where the tiles differ enough in work to pay for it: the order breaks up the
-    // XCD runs' spatial adjacency (neighbouring tiles share records in one L2), which on the uniform benchmark scene cost
-    // +39 % HBM traffic in render_bwd (594 instead of 428 MB, profiles/r04_pmc_summary_all_tiles_ordered.json) for 2 % of
-    // its time; on a skewed scene (garden-shaped workload: longest list 7x the average) it is worth 6.5 %.  Decided like
-    // the rest of the queued tail by the previous forward's figures.
-    const bool ordered = !ro && gs::tile_order_supported(num_tiles) && !gs_no_tile_order() && c->last_longest > 0 &&
-                         c->S > 0 && c->last_longest * (long long)num_tiles > 3ll * (long long)c->S;
-    // (The forward itself keeps the plain XCD-run order: dealt heaviest first by list length it was 10-14 us SLOWER on
-    // the garden-shaped workload, profiles/r04_tile_order_ab.txt -- the list length says little about a dense tile's
-    // forward, whose pixels saturate early, and neighbouring tiles no longer run side by side on one XCD's L2.)
-    // Lists beyond kSegSplitMin are split for the backward (gs_render.h: TileSegments) -- decided, like the order, by the
-    // previous forward: its longest list says whether there is anything to split; the room for extra blocks follows what
-    // the tiles of the previous forward asked for (a list that does not fit stays whole).
-    // r06: the figures the segment kernels publish -- how uneven the tiles' work is, how many segments the
-    // lists asked for -- decide whether THIS forward splits and how much room it reserves, and a split forward sums
-    // per-segment partials where an unsplit one runs one fma chain: the decision must not follow host / GPU timing.
-    // The kernels write each figure as {ticket << 32 | value} into the slot of their forward's ticket parity.  This
-    // forward (ticket t) takes the slot of ticket t - 2: the host has seen the record of forward t - 1, which
-    // bin_scatter_kernel published BEHIND everything forward t - 2 queued on the stream, so that slot is complete -- and
-    // nobody writes it again before this forward's own kernels, queued below, run.  (The figures of forward t - 1 may or
-    // may not have landed yet: they are never looked at.)  A slot that does not carry ticket t - 2 -- the forward two back
-    // published nothing -- leaves the figures as they were.
-    {
-      const unsigned int want_tag = (unsigned int)((ticket - 2) & 0xFFFFFFFFull);
-      const volatile unsigned long long *slot = c->h_pub + 8 + 4 * (ticket & 1ull);
-      const unsigned long long w0 = __atomic_load_n(&slot[0], __ATOMIC_RELAXED), w1 = __atomic_load_n(&slot[1], __ATOMIC_RELAXED);
-      const unsigned long long w2 = __atomic_load_n(&slot[2], __ATOMIC_RELAXED), w3 = __atomic_load_n(&slot[3], __ATOMIC_RELAXED);
-      if (ticket >= 3 && (unsigned int)(w0 >> 32) == want_tag && (unsigned int)(w1 >> 32) == want_tag) {
-        c->fig_max = (long long)(int)(unsigned int)w0;
-        c->fig_sum = (long long)(int)(unsigned int)w1;
-      }
-      if (ticket >= 3 && (unsigned int)(w2 >> 32) == want_tag) c->fig_asked_bwd = (long long)(int)(unsigned int)w2;
-      if (ticket >= 3 && (unsigned int)(w3 >> 32) == want_tag) c->fig_asked_fwd = (long long)(int)(unsigned int)w3;
-    }
-    unsigned long long *d_slot = c->d_pub + 8 + 4 * (ticket & 1ull);  // where THIS forward's kernels publish
-    const unsigned int my_tag = (unsigned int)(ticket & 0xFFFFFFFFull);
-    gs::TileSegments seg = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, my_tag};
-    const bool split = !ro && !gs_no_segments() && c->last_longest > gs::kSegSplitMin && num_tiles <= 16384;  // (the table kernels' reach)
-    if (split) {
-      const size_t slots = cap / gs::kSegEntries + 2;  // (gs_render.h: segment_slot)
-      const size_t asked = (size_t)c->fig_asked_bwd;
-      const size_t want = std::min(slots, (asked + asked / 2 + 256 + 7) & ~(size_t)7);
-      if ((r = c->seg_first.reserve(((size_t)num_tiles + 8) * 4))) return r;
-      if ((r = c->seg_extra.reserve((want + 2) * sizeof(int2)))) return r;  // [want]: the count
-      if ((r = c->seg_chk.reserve(slots * 256 * sizeof(float4)))) return r;
-      if (c->depth && (r = c->seg_chk_d.reserve(slots * 256 * sizeof(float)))) return r;
-      seg = {c->seg_first.as<int>(), c->seg_extra.as<int2>(), reinterpret_cast<int *>(c->seg_extra.as<int2>() + want),
-             c->seg_chk.as<float4>(), c->image.as<float>(), (int)want, d_slot + 2, nullptr, my_tag};
-    }
-    // the tiles' largest stop indices of this forward, for the next one's decision below
-    const bool figures = !gs_no_fwd_segments() && c->last_longest > gs::kSegSplitMin && num_tiles <= 16384;
-    if (figures) seg.stats = d_slot;
-    // ... and for the forward itself (gs_render.h: FwdSegments): every segment of a long list a block of its own
-    gs::FwdSegments fs = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, my_tag, nullptr, 0, 0};
-    // Only where the tiles' work is uneven enough for ONE list to set the launch's duration: the previous forward's longest
-    // chain (the largest stop index of any tile) against the work per resident workgroup (the sum over the tiles / 2048).
-    // A throughput-bound scene gains nothing from the split and pays for its table, its combine pass and the product passes
-    // (garden-shaped synthetic scene 0.197 -> 0.271 ms, dense4m 0.183 -> 0.26 when split regardless).
-    const long long top_max = c->fig_max, top_sum = c->fig_sum;
-    const double gate = c->fseg_gate >= 0.0 ? c->fseg_gate : gs_fwd_segments_gate();
-    const bool fsplit = figures && top_sum > 0 && top_max * 2048ll > (long long)(gate * (double)top_sum);
-    if (fsplit) {
-      const size_t most = cap / gs::kSegEntries + (size_t)num_tiles + 8;  // sum of ceil(len / kSegEntries) over any lists
-      const size_t asked = (size_t)c->fig_asked_fwd;
-      const size_t want = std::min(most, asked + asked / 4 + 512) + 7 & ~(size_t)7;
-      if ((r = c->fseg_first.reserve(((size_t)num_tiles + 8 + 136) * 4))) return r;  // ranks | layer bases
-      if ((r = c->fseg_blocks.reserve((want + 2) * sizeof(int2)))) return r;  // [want]: the count
-      if ((r = c->fseg_gran.reserve(2 * want * 256 * sizeof(unsigned long long)))) return r;  // t products | final Ts
-      if ((r = c->fseg_part.reserve(want * 256 * sizeof(float4)))) return r;
-      if (c->depth && (r = c->fseg_part_d.reserve(want * 256 * sizeof(float)))) return r;
-      if ((r = c->fseg_stop.reserve(want * 256 * sizeof(int)))) return r;
-      if (c->fseg_gran.ptr != c->fseg_gran_zeroed || c->fseg_gran.bytes != c->fseg_gran_zeroed_bytes) {
-        GS_HIP(hipMemsetAsync(c->fseg_gran.ptr, 0, c->fseg_gran.bytes, st));  // tags of no epoch
-        c->fseg_gran_zeroed = c->fseg_gran.ptr;
-        c->fseg_gran_zeroed_bytes = c->fseg_gran.bytes;
-      }
-      if (++c->fseg_epoch == 0) c->fseg_epoch = 1;
-      fs = {c->fseg_first.as<int>(), c->fseg_first.as<int>() + num_tiles + 8, c->fseg_blocks.as<int2>(),
-            reinterpret_cast<int *>(c->fseg_blocks.as<int2>() + want),
-            c->fseg_gran.as<unsigned long long>(), c->fseg_part.as<float4>(), c->fseg_stop.as<int>(), (int)want,
-            c->fseg_epoch, d_slot + 3, my_tag, c->fseg_fallbacks(), c->fseg_poll_budget, c->fseg_thin_layer};
-      if ((r = gs::launch_fwd_segments_table(c->ranges.as<int>(), num_tiles, fs, st))) return r;
-      segmented_this_forward = true;  // (counted once per forward below: a redone tail comes through here twice)
-    }
-    if (join_pending) GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));  // (late join: the records' colour is first read here)
-    gs::DepthMaps dm = dmap;
-    if (c->depth) {
-      dm.chk = split ? c->seg_chk_d.as<float>() : nullptr;
-      dm.part = fsplit ? c->fseg_part_d.as<float>() : nullptr;
-    }
-    r = gs::launch_render_fwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(), W, H, bg_color,
-                              c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
-                              c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)N * 4,  // M <= N is not known here yet
-                              ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr,
-                              (ordered || split || figures) ? c->tile_tops.as<int>() : nullptr, split ? &seg : nullptr,
-                              fsplit ? &fs : nullptr, c->depth ? &dm : nullptr);
-    if (r) return r;
-    c->seg_ready = split;
-    c->seg_cap = seg.extra_cap;
-    c->mark(4, true, st);
-    // the backward's tile order, behind the forward: nothing waits for it until the loss has produced dL/dimage
-    if (ordered && (r = gs::launch_tile_order(c->tile_tops.as<int>(), nullptr, num_tiles, c->tile_order.as<int>(), st))) return r;
-    c->order_ready = ordered;
-    // ... and which segments of the long lists get a block of their own
-    if ((split || figures) && (r = gs::launch_tile_segments(c->ranges.as<int>(), c->tile_tops.as<int>(), num_tiles, seg, st))) return r;
-    return GSPLAT_OK;
-  };
-  // once a backward has been seen, the forward clears the gradient rows on the side (see render_fwd_kernel)
-  if (c->rows_zeroed) c->backward_seen = false;  // the last forward's cleared rows were never used: rendering only
-  c->rows_zeroed = c->backward_seen && !ro;
-  long long spec_hint = -1;
-  if (sparse) {
-    // `ranges` on the device are clamped to spec_cap (bin_scatter_kernel): whatever S turns out to be, the queued kernels
-    // stay inside the buffers
-    spec_hint = c->last_longest >= 0 ? c->last_longest + c->last_longest / 2 + 64 : -1;  // unknown: every kernel
-    if ((rc = queue_tail(spec_cap, spec_hint, true))) return rc;
+  if ((longest_hint < 0 || longest_hint > 2048) && !c->fork.ready) {  // lists beyond two register-sorted runs: see SortFork
+    const int fr = c->fork.create();
+    if (fr) return fr;
   }
-  {
-    // Poll the mapped record; every few hundred polls ask the runtime about the stream, which both keeps its
-    // submission path moving and tells us when everything queued so far has drained.
-    volatile unsigned long long *pub = c->h_pub;
-    auto arrived = [&]() {
-      for (int k = 0; k < gs::kRecordWords; ++k)
-        if ((__atomic_load_n(&pub[k], __ATOMIC_RELAXED) & 0xFFFFFFFFull) != (ticket & 0xFFFFFFFFull)) return false;
-      __atomic_thread_fence(__ATOMIC_ACQUIRE);
-      return true;
-    };
-    long long polls = 0;
-    while (!arrived()) {
-      if ((++polls & 255) == 0) {
-        const hipError_t q = hipStreamQuery(st);
-        if (q == hipSuccess) {  // stream drained: the record must be there now
-          if (arrived()) break;
-          gs::set_error("gsplat_rasterize_image: the count record never arrived");
-          return GSPLAT_ERR_HIP;
-        }
-        if (q != hipErrorNotReady) {
-          gs::set_error("gsplat_rasterize_image: %s while waiting for the counts", hipGetErrorString(q));
-          return GSPLAT_ERR_HIP;
-        }
-      }
-      __builtin_ia32_pause();
-    }
+  int r = gs::binning_scatter_and_sort(c->uv.as<float>(), c->xyz_c.as<float>(), c->radius.as<float>(),
+                                       c->hitmask.as<unsigned long long>(), c->rank.as<int>(), f.N, f.ntx, f.nty,
+                                       c->bin_table.as<int>(), c->ranges.as<int>(), cap, c->pay_a.as<unsigned long long>(),
+                                       c->keys_a.as<int>(), c->sorted.as<int>(), longest_hint, c->rank.as<int>() + f.N,
+                                       c->pair_counters(), publish ? c->d_pub : nullptr, f.ticket, st, &c->fork, f.compact,
+                                       f.keys_ok);
+  if (r) return r;
+  c->mark(2, true, st);
+  c->mark(4, false, st);
+  // Everything below is decided, like the kernels queued above, by the previous forward's figures (the rules and what
+  // they were measured against: gs_forward_plan.h).  Heaviest-first tiles for the backward:
+  const bool ordered = !ro && gs::tile_order_supported(num_tiles) && !gs_no_tile_order() &&
+                       gs::tile_order_pays(c->last_longest, num_tiles, c->S);
+  // Lists beyond kSegSplitMin are split for the backward (gs_render.h: TileSegments): the previous forward's longest list
+  // says whether there is anything to split; the room for extra blocks follows what its tiles asked for (a list that
+  // does not fit stays whole).  The figures the segment kernels publish (gs::take_figures):
+  const volatile unsigned long long *h_slot = c->h_pub + 8 + 4 * (f.ticket & 1ull);
+  unsigned long long w[4];
+  for (int k = 0; k < 4; ++k) w[k] = __atomic_load_n(&h_slot[k], __ATOMIC_RELAXED);
+  gs::take_figures(w, f.ticket, c->fig);
+  unsigned long long *d_slot = c->d_pub + 8 + 4 * (f.ticket & 1ull);  // where THIS forward's kernels publish
+  const unsigned int my_tag = (unsigned int)(f.ticket & 0xFFFFFFFFull);
+  gs::TileSegments seg = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, my_tag};
+  const bool split = !ro && !gs_no_segments() && c->last_longest > gs::kSegSplitMin && num_tiles <= 16384;  // (the table kernels' reach)
+  if (split) {
+    const size_t slots = cap / gs::kSegEntries + 2;  // (gs_render.h: segment_slot)
+    const size_t want = gs::bwd_segment_room(cap, (size_t)c->fig.asked_bwd, gs::kSegEntries);
+    if ((r = c->seg_first.reserve(((size_t)num_tiles + 8) * 4))) return r;
+    if ((r = c->seg_extra.reserve((want + 2) * sizeof(int2)))) return r;  // [want]: the count
+    if ((r = c->seg_chk.reserve(slots * 256 * sizeof(float4)))) return r;
+    if (c->depth && (r = c->seg_chk_d.reserve(slots * 256 * sizeof(float)))) return r;
+    seg = {c->seg_first.as<int>(), c->seg_extra.as<int2>(), reinterpret_cast<int *>(c->seg_extra.as<int2>() + want),
+           c->seg_chk.as<float4>(), c->image.as<float>(), (int)want, d_slot + 2, nullptr, my_tag};
   }
-  const int M = (int)(unsigned int)(c->h_pub[0] >> 32);
-  const size_t S = (size_t)(c->h_pub[1] >> 32);
-  const unsigned long long pairs = (c->h_pub[2] >> 32) | (c->h_pub[3] & 0xFFFFFFFF00000000ull);
-  if (M == 0) {
+  // the tiles' largest stop indices of this forward, for the next one's decision below
+  const bool figures = !gs_no_fwd_segments() && c->last_longest > gs::kSegSplitMin && num_tiles <= 16384;
+  if (figures) seg.stats = d_slot;
+  // ... and for the forward itself (gs_render.h: FwdSegments): every segment of a long list a block of its own, only
+  // where the tiles' work is uneven enough
+  gs::FwdSegments fs = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, my_tag, nullptr, 0, 0};
+  const double gate = c->fseg_gate >= 0.0 ? c->fseg_gate : gs_fwd_segments_gate();
+  const bool fsplit = figures && gs::forward_split_pays(c->fig.max, c->fig.sum, gate);
+  if (fsplit) {
+    const size_t want = gs::fwd_segment_room(cap, num_tiles, (size_t)c->fig.asked_fwd, gs::kSegEntries);
+    if ((r = c->fseg_first.reserve(((size_t)num_tiles + 8 + 136) * 4))) return r;  // ranks | layer bases
+    if ((r = c->fseg_blocks.reserve((want + 2) * sizeof(int2)))) return r;  // [want]: the count
+    if ((r = c->fseg_gran.reserve(2 * want * 256 * sizeof(unsigned long long)))) return r;  // t products | final Ts
+    if ((r = c->fseg_part.reserve(want * 256 * sizeof(float4)))) return r;
+    if (c->depth && (r = c->fseg_part_d.reserve(want * 256 * sizeof(float)))) return r;
+    if ((r = c->fseg_stop.reserve(want * 256 * sizeof(int)))) return r;
+    if (c->fseg_gran.ptr != c->fseg_gran_zeroed || c->fseg_gran.bytes != c->fseg_gran_zeroed_bytes) {
+      GS_HIP(hipMemsetAsync(c->fseg_gran.ptr, 0, c->fseg_gran.bytes, st));  // tags of no epoch
+      c->fseg_gran_zeroed = c->fseg_gran.ptr;
+      c->fseg_gran_zeroed_bytes = c->fseg_gran.bytes;
+    }
+    if (++c->fseg_epoch == 0) c->fseg_epoch = 1;
+    fs = {c->fseg_first.as<int>(), c->fseg_first.as<int>() + num_tiles + 8, c->fseg_blocks.as<int2>(),
+          reinterpret_cast<int *>(c->fseg_blocks.as<int2>() + want),
+          c->fseg_gran.as<unsigned long long>(), c->fseg_part.as<float4>(), c->fseg_stop.as<int>(), (int)want,
+          c->fseg_epoch, d_slot + 3, my_tag, c->fseg_fallbacks(), c->fseg_poll_budget, c->fseg_thin_layer};
+    if ((r = gs::launch_fwd_segments_table(c->ranges.as<int>(), num_tiles, fs, st))) return r;
+    f.segmented_this_forward = true;  // (counted once per forward: a redone tail comes through here twice)
+  }
+  if (f.join_pending) GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));  // (late join: the records' colour is first read here)
+  gs::DepthMaps dm = f.dmap;
+  if (c->depth) {
+    dm.chk = split ? c->seg_chk_d.as<float>() : nullptr;
+    dm.part = fsplit ? c->fseg_part_d.as<float>() : nullptr;
+  }
+  r = gs::launch_render_fwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(), f.W, f.H, f.bg,
+                            c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
+                            c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)f.N * 4,  // M <= N is not known here yet
+                            ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr,
+                            (ordered || split || figures) ? c->tile_tops.as<int>() : nullptr, split ? &seg : nullptr,
+                            fsplit ? &fs : nullptr, c->depth ? &dm : nullptr);
+  if (r) return r;
+  c->seg_ready = split;
+  c->seg_cap = seg.extra_cap;
+  c->mark(4, true, st);
+  // the backward's tile order, behind the forward: nothing waits for it until the loss has produced dL/dimage
+  if (ordered && (r = gs::launch_tile_order(c->tile_tops.as<int>(), nullptr, num_tiles, c->tile_order.as<int>(), st))) return r;
+  c->order_ready = ordered;
+  // ... and which segments of the long lists get a block of their own
+  if ((split || figures) && (r = gs::launch_tile_segments(c->ranges.as<int>(), c->tile_tops.as<int>(), num_tiles, seg, st))) return r;
+  return GSPLAT_OK;
+}
+
+// The one host read-back of the forward: poll the mapped record; every few hundred polls ask the runtime about the
+// stream, which both keeps its submission path moving and tells us when everything queued so far has drained.
+static int wait_for_record(gsplat_context *c, const FwdCall &f, gs::ForwardRecord &rec) {
+  unsigned long long w[gs::kRecordWords];
+  bool drained = false;
+  for (long long polls = 1;; ++polls) {
+    for (int k = 0; k < gs::kRecordWords; ++k) w[k] = __atomic_load_n(&c->h_pub[k], __ATOMIC_RELAXED);
+    if (gs::record_arrived(w, f.ticket)) break;
+    if (drained) {  // the stream had drained before these loads: the record would be there
+      gs::set_error("gsplat_rasterize_image: the count record never arrived");
+      return GSPLAT_ERR_HIP;
+    }
+    if ((polls & 255) == 0) {
+      const hipError_t q = hipStreamQuery(f.st);
+      if (q != hipSuccess && q != hipErrorNotReady) {
+        gs::set_error("gsplat_rasterize_image: %s while waiting for the counts", hipGetErrorString(q));
+        return GSPLAT_ERR_HIP;
+      }
+      if ((drained = q == hipSuccess)) continue;  // look once more, at once
+    }
+    __builtin_ia32_pause();
+  }
+  __atomic_thread_fence(__ATOMIC_ACQUIRE);
+  rec = gs::decode_record(w);
+  if (!f.sparse) rec.longest = -1;  // (the radix route does not know it)
+  if (rec.M == 0) {
     gs::set_error("gsplat_rasterize_image: no gaussians in view");  // cuda/raster.cu:38-41
     return GSPLAT_ERR_NO_VISIBLE;
   }
-  const long long longest = sparse ? (long long)(c->h_pub[4] >> 32) : -1;
-  c->dense_route = gs::binning_next_route_is_radix(sparse, S, num_tiles, longest);
-  c->last_longest = longest;
-  const bool emitted = S <= inst_cap;  // dense route: else grow the instance buffers (synchronises) and emit again
-  c->n_forwards++;
-  if (compact) c->n_compact_walks++;
-  if (sparse) {
-    const bool fits = S <= spec_cap;
-    if (!fits || !(spec_hint < 0 || list_class(longest) <= list_class(spec_hint))) {
-      c->n_tail_redone++;
-      if (!fits) c->n_instance_growths++;
-      // grow (synchronises); the placement queued below writes the true ranges
-      if (!fits && (rc = reserve_instances(c, S + S / 4, num_tiles, st))) return rc;
-      // the long-tile counter lives at the head of keys_a: zeroed by bin_offsets, then used by the queued sorts
-      GS_HIP(hipMemsetAsync(c->keys_a.ptr, 0, sizeof(int), st));
-      if ((rc = queue_tail(S, longest, false))) return rc;
-    }
-  } else {
-    if ((rc = reserve_instances(c, S, num_tiles, st))) return rc;
-    if (S + 1 > instance_room(c)) {
-      gs::set_error("gsplat_rasterize_image: internal: %zu instances sorted in room for %zu", S, instance_room(c));
-      return GSPLAT_ERR_CAPACITY;
-    }
-    rc = gs::emit_sort_ranges(c->uv.as<float>(), c->xyz_c.as<float>(), c->radius.as<float>(), ntx, nty, N,
-                              c->mask.as<unsigned char>(), c->rank.as<int>(), c->offsets.as<int>(), S,
-                              c->keys_a.as<unsigned int>(), c->keys_b.as<unsigned int>(),
-                              c->pay_a.as<unsigned long long>(), c->pay_b.as<unsigned long long>(),
-                              c->sorted.as<int>(), c->ranges.as<int>(), c->temp.ptr, c->temp.bytes, st, emitted,
-                              c->hitmask.as<unsigned long long>());
-    if (rc) return rc;
-    c->mark(2, true, st);
-    c->mark(4, false, st);
-    const bool ordered = false;  // (radix route: the longest list is not known; see queue_tail)
-    if (join_pending) GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));
-    rc = gs::launch_render_fwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(), W, H, bg_color,
-                               c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
-                               c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)M * 4,
-                               ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr,
-                               ordered ? c->tile_tops.as<int>() : nullptr, nullptr, nullptr, c->depth ? &dmap : nullptr);
-    if (rc) return rc;
-    c->seg_ready = false;
-    c->mark(4, true, st);
-    if (ordered && (rc = gs::launch_tile_order(c->tile_tops.as<int>(), nullptr, num_tiles, c->tile_order.as<int>(), st))) return rc;
-    c->order_ready = ordered;
+  return GSPLAT_OK;
+}
+
+// Radix route behind the record: grow the instance buffers if S outgrew them (synchronises) and emit again; sort, ranges, compositing
+static int finish_radix_route(gsplat_context *c, const FwdCall &f, const gs::ForwardRecord &rec, size_t inst_cap) {
+  const size_t S = rec.S; hipStream_t st = f.st;
+  int rc = reserve_instances(c, S, f.num_tiles, st);
+  if (rc) return rc;
+  if (S + 1 > instance_room(c)) {
+    gs::set_error("gsplat_rasterize_image: internal: %zu instances sorted in room for %zu", S, instance_room(c));
+    return GSPLAT_ERR_CAPACITY;
   }
-  if (segmented_this_forward) c->n_segmented_forwards++;
-  c->N = N; c->M = M; c->S = S; c->l_max = l_max; c->width = W; c->height = H;
+  rc = gs::emit_sort_ranges(c->uv.as<float>(), c->xyz_c.as<float>(), c->radius.as<float>(), f.ntx, f.nty, f.N,
+                            c->mask.as<unsigned char>(), c->rank.as<int>(), c->offsets.as<int>(), S,
+                            c->keys_a.as<unsigned int>(), c->keys_b.as<unsigned int>(),
+                            c->pay_a.as<unsigned long long>(), c->pay_b.as<unsigned long long>(),
+                            c->sorted.as<int>(), c->ranges.as<int>(), c->temp.ptr, c->temp.bytes, st, S <= inst_cap,
+                            c->hitmask.as<unsigned long long>());
+  if (rc) return rc;
+  c->mark(2, true, st);
+  c->mark(4, false, st);
+  if (f.join_pending) GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));
+  // (no tile order on this route: the longest list is not known; see queue_sparse_tail)
+  rc = gs::launch_render_fwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(), f.W, f.H, f.bg,
+                             c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
+                             c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)rec.M * 4,
+                             f.ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr, nullptr, nullptr, nullptr,
+                             c->depth ? &f.dmap : nullptr);
+  if (rc) return rc;
+  c->seg_ready = false;
+  c->mark(4, true, st);
+  c->order_ready = false;
+  return GSPLAT_OK;
+}
+
+// The forward is recorded in the context (what the backward entry points check against) and described to the caller
+static void record_forward(gsplat_context *c, const FwdCall &f, const gs::ForwardRecord &rec, gsplat_forward_view *out) {
+  if (f.segmented_this_forward) c->n_segmented_forwards++;
+  c->N = f.N; c->M = rec.M; c->S = rec.S; c->l_max = f.l_max; c->width = f.W; c->height = f.H;
   c->last_mask = c->mask.as<unsigned char>();
   gs::pool_watch(c->last_mask, &c->last_mask);  // cleared when whoever ends up owning the block returns it to the pool
-  c->tan_fovx = tan_fovx; c->tan_fovy = tan_fovy; c->mh_dist = cfg->mh_dist;
-  c->have_forward = !ro;  // a render-only forward leaves nothing for a backward
+  c->tan_fovx = f.tan_fovx; c->tan_fovy = f.tan_fovy; c->mh_dist = f.cfg->mh_dist;
+  c->have_forward = !f.ro;  // a render-only forward leaves nothing for a backward
   c->depth_ready = c->depth;
-  if (out) {
-    out->num_culled = (size_t)M; out->num_pairs = (size_t)pairs; out->num_splats = S;
-    out->mask = c->mask.as<unsigned char>();
-    out->uv = c->lean ? nullptr : c->uv_all.as<float>(); out->xyz_c = c->lean ? nullptr : c->xyz_c_all.as<float>();
-    out->compact_to_global = c->c2g.as<int>();
-    out->sigma = mid ? c->sigma.as<float>() : nullptr; out->conic = mid ? c->conic.as<float>() : nullptr;
-    out->J = mid ? c->J.as<float>() : nullptr; out->precomputed_rgb = mid ? c->rgb.as<float>() : nullptr;
-    out->radius = c->radius.as<float>();
-    out->uv_selected = c->uv.as<float>(); out->xyz_c_selected = c->xyz_c.as<float>();
-    out->sorted_gaussians = c->sorted.as<int>();
-    out->splat_start_end_idx_by_tile_idx = c->ranges.as<int>();
-    out->image = c->image.as<float>(); out->weight_per_pixel = c->T_px.as<float>();
-    out->splats_per_pixel = c->n_px.as<int>();
+  if (!out) return;
+  const bool mid = f.mid;
+  out->num_culled = (size_t)rec.M; out->num_pairs = (size_t)rec.pairs; out->num_splats = rec.S;
+  out->mask = c->mask.as<unsigned char>(); out->compact_to_global = c->c2g.as<int>();
+  out->uv = c->lean ? nullptr : c->uv_all.as<float>(); out->xyz_c = c->lean ? nullptr : c->xyz_c_all.as<float>();
+  out->sigma = mid ? c->sigma.as<float>() : nullptr; out->conic = mid ? c->conic.as<float>() : nullptr;
+  out->J = mid ? c->J.as<float>() : nullptr; out->precomputed_rgb = mid ? c->rgb.as<float>() : nullptr;
+  out->radius = c->radius.as<float>(); out->uv_selected = c->uv.as<float>(); out->xyz_c_selected = c->xyz_c.as<float>();
+  out->sorted_gaussians = c->sorted.as<int>(); out->splat_start_end_idx_by_tile_idx = c->ranges.as<int>();
+  out->image = c->image.as<float>(); out->weight_per_pixel = c->T_px.as<float>();
+  out->splats_per_pixel = c->n_px.as<int>();
+}
+
+int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                           const gsplat_raster_config *cfg, float bg_color, int l_max, gsplat_forward_view *out,
+                           void *stream) {
+  int rc = check_forward_args(c, g, cam, cfg, l_max);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = reclaim_outputs(c, st))) return rc;
+  FwdCall f;
+  if ((rc = plan_forward_call(c, g, cam, cfg, bg_color, l_max, st, f))) return rc;
+  if (c->timing) {  // next timing slot; its events are >= kSlots forwards old, hence complete
+    c->slot = (int)(c->fwd_calls % gsplat_context::kSlots);
+    c->harvest(c->slot);
   }
+  c->fwd_calls++;
+  if ((rc = launch_cull(c, f))) return rc;
+  if ((rc = launch_per_gaussian(c, f))) return rc;
+  size_t room = 0;  // of the instance buffers: what the kernels queued before the wait may use
+  if ((rc = queue_counts(c, f, room))) return rc;
+  // once a backward has been seen, the forward clears the gradient rows on the side (see render_fwd_kernel)
+  if (c->rows_zeroed) c->backward_seen = false;  // the last forward's cleared rows were never used: rendering only
+  c->rows_zeroed = c->backward_seen && !f.ro;
+  const long long spec_hint = f.sparse ? gs::speculative_longest(c->last_longest) : -1;
+  if (f.sparse && (rc = queue_sparse_tail(c, f, room, spec_hint, true))) return rc;
+  gs::ForwardRecord rec;
+  if ((rc = wait_for_record(c, f, rec))) return rc;
+  c->dense_route = gs::binning_next_route_is_radix(f.sparse, rec.S, f.num_tiles, rec.longest);
+  c->last_longest = rec.longest;
+  c->n_forwards++;
+  if (f.compact) c->n_compact_walks++;
+  if (!f.sparse) {
+    if ((rc = finish_radix_route(c, f, rec, room))) return rc;
+  } else if (gs::tail_needs_redo(rec.S, room, spec_hint, rec.longest, f.keys_ok)) {
+    c->n_tail_redone++;
+    if (rec.S > room) {  // grow (synchronises); the placement queued below writes the true ranges
+      c->n_instance_growths++;
+      if ((rc = reserve_instances(c, rec.S + rec.S / 4, f.num_tiles, st))) return rc;
+    }
+    // the long-tile counter lives at the head of keys_a: zeroed by bin_offsets, then used by the queued sorts
+    GS_HIP(hipMemsetAsync(c->keys_a.ptr, 0, sizeof(int), st));
+    if ((rc = queue_sparse_tail(c, f, rec.S, rec.longest, false))) return rc;
+  }
+  record_forward(c, f, rec, out);
   return GSPLAT_OK;
 }
 
@@ -2555,117 +2557,67 @@ int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, con
   return GSPLAT_OK;
 }
 
-int gsplat_backward_gaussians(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
-                              const gsplat_gradients *out, void *stream) {
-  return gsplat_backward_gaussians_range(c, g, cam, l_max, out, 0, g ? g->num_gaussians : 0, stream);
+// ---- Checks the backward entry points share.  `fn` is the public function the caller called: the error text's prefix.
+// A forward is recorded and the arguments are the ones it ran with
+static int check_recorded_forward(const char *fn, const gsplat_context *c, const gsplat_gaussians *g,
+                                  const gsplat_camera *cam, int l_max) {
+  GS_REQUIRE_IN(fn, c->have_forward, "no forward pass recorded in this context");
+  GS_REQUIRE_IN(fn, l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
+                "backward arguments do not match the recorded forward pass");
+  return GSPLAT_OK;
 }
 
-static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
-                                   const gsplat_gradients *out, float *common, float *uv_norm, int first_gaussian,
-                                   int end_gaussian, void *stream, const AdamFused *adam = nullptr, int adam_mode = 2,
-                                   float *grad_view = nullptr, float *grad_campos = nullptr);
-
-int gsplat_backward_gaussians_range(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
-                                    const gsplat_gradients *out, int first_gaussian, int end_gaussian, void *stream) {
-  GS_REQUIRE(out != nullptr, "null argument struct");
-  return backward_gaussians_impl(c, g, cam, l_max, out, nullptr, nullptr, first_gaussian, end_gaussian, stream);
-}
-
-int gsplat_backward_gaussians_split(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
-                                    float *common, float *uv_norm, int first_gaussian, int end_gaussian, void *stream) {
-  GS_REQUIRE_DEV(common);
-  GS_REQUIRE(((uintptr_t)common & 15) == 0, "common must be 16-byte aligned");
-  if (uv_norm) GS_REQUIRE_DEV(uv_norm);
-  return backward_gaussians_impl(c, g, cam, l_max, nullptr, common, uv_norm, first_gaussian, end_gaussian, stream);
-}
-
-int gsplat_backward_gaussians_adam(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
-                                   const gsplat_adam_fused *opt, const gsplat_gradients *out, void *stream) {
-  GS_REQUIRE(opt != nullptr && g != nullptr, "null argument struct");
-  GS_REQUIRE(!(c && c->have_forward && c->fwd_antialiased),
-             "the forward ran in anti-aliased mode: the Adam-inside backward steps the opacity before the covariance chain "
-             "exists (use gsplat_backward_gaussians and the optimizer kernels)");
-  const int n_groups = l_max > 0 ? 6 : 5;
-  for (int k = 0; k < 6; ++k) {
-    if (k == 2 && l_max == 0) continue;  // no coefficients beyond band 0
-    GS_REQUIRE_DEV(opt->exp_avg[k]); GS_REQUIRE_DEV(opt->exp_avg_sq[k]);
+// The gradient arrays of `out`: the five leaves (where the form stores them) and the optional SH array
+static int check_gradient_arrays(const char *fn, const gsplat_gradients *out, int l_max, bool leaves = true) {
+  if (leaves) {
+    GS_REQUIRE_DEV_IN(fn, out->grad_xyz); GS_REQUIRE_DEV_IN(fn, out->grad_rgb); GS_REQUIRE_DEV_IN(fn, out->grad_opacity);
+    GS_REQUIRE_DEV_IN(fn, out->grad_scale); GS_REQUIRE_DEV_IN(fn, out->grad_quaternion);
+    GS_REQUIRE_IN(fn, ((uintptr_t)out->grad_quaternion & 15) == 0, "grad_quaternion must be 16-byte aligned");
   }
-  (void)n_groups;
-  GS_REQUIRE(((uintptr_t)opt->exp_avg[5] & 15) == 0 && ((uintptr_t)opt->exp_avg_sq[5] & 15) == 0,
-             "the quaternion moments must be 16-byte aligned");
-  if (opt->uv_grad_accum) GS_REQUIRE_DEV(opt->uv_grad_accum);
-  if (opt->grad_accum_dur) GS_REQUIRE_DEV(opt->grad_accum_dur);
-  AdamFused ad = {opt->exp_avg[0], opt->exp_avg_sq[0], opt->exp_avg[1], opt->exp_avg_sq[1], opt->exp_avg[2], opt->exp_avg_sq[2],
-                  opt->exp_avg[3], opt->exp_avg_sq[3], opt->exp_avg[4], opt->exp_avg_sq[4], opt->exp_avg[5], opt->exp_avg_sq[5],
-                  opt->lr[0], opt->lr[1], opt->lr[2], opt->lr[3], opt->lr[4], opt->lr[5],
-                  opt->b1, opt->b2, opt->eps, opt->bias1, opt->bias2, opt->uv_grad_accum, opt->grad_accum_dur, nullptr};
-  GS_REQUIRE(opt->mode >= 0 && opt->mode <= 2,
-             "mode: 0 all six groups in one kernel, 1 SH and position left to the optimizer kernels, 2 the SH group in a kernel of its own in front");
-  if (opt->mode == 1) {
-    GS_REQUIRE(out != nullptr, "mode 1 hands grad_xyz and grad_precompute_rgb to the optimizer kernels: `out` is needed");
-    GS_REQUIRE_DEV(out->grad_xyz);
-    if (l_max > 0) GS_REQUIRE_DEV(out->grad_precompute_rgb);
-  }
-  if (opt->mode == 2 && l_max > 0 && c && c->have_forward && c->M > 0) {
-    // the SH rows are read ONCE, by sh_adam_dir_kernel: their Adam step and sh_bwd's sums over them; the per-gaussian
-    // backward behind it (kAdam 3) takes the position gradient through the view direction from c->dir_grad
-    GS_REQUIRE(c->rows_ready, "gsplat_backward_render has not run for this forward pass");
-    GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N, "backward arguments do not match the recorded forward pass");
-    GS_REQUIRE(cam != nullptr, "null argument struct");
-    hipStream_t st = (hipStream_t)stream;
-    int rc = c->dir_grad.reserve((size_t)c->M * 3 * sizeof(float), st);
-    if (rc) return rc;
-    ad.dir = c->dir_grad.as<float>();
-    const unsigned int blocks = (unsigned int)(((long long)c->M * 16 + kBlock - 1) / kBlock);
-    float *sh_p = const_cast<float *>(g->sh);
-#define GS_SHA(LL)                                                                                                     \
-  sh_adam_dir_kernel<LL><<<blocks, kBlock, 0, st>>>(c->M, c->c2g.as<int>(), sh_p, ad.m_sh, ad.v_sh, ad.lr_sh, ad.b1, ad.b2,  \
-                                                   ad.eps, ad.bias1, ad.bias2, g->xyz, g->rgb, cam->campos[0], cam->campos[1], \
-                                                   cam->campos[2], c->grad_rows.as<float4>(), ad.dir)
-    switch (l_max) {
-      case 1: GS_SHA(1); break;
-      case 2: GS_SHA(2); break;
-      default: GS_SHA(3); break;
-    }
-#undef GS_SHA
-    GS_LAUNCH_CHECK();
-  }
-  return backward_gaussians_impl(c, g, cam, l_max, out, nullptr, nullptr, 0, g->num_gaussians, stream, &ad,
-                                 opt->mode == 1 ? 1 : opt->mode == 2 ? 3 : 2);
+  if (l_max > 0 && out->grad_sh) GS_REQUIRE_DEV_IN(fn, out->grad_sh);  // NULL: the caller rebuilds them (gsplat_optimizer_step_sh_factored)
+  return GSPLAT_OK;
 }
 
-static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
-                                   const gsplat_gradients *out, float *common, float *uv_norm, int first_gaussian,
-                                   int end_gaussian, void *stream, const AdamFused *adam, int adam_mode,
-                                   float *grad_view, float *grad_campos) {
-  GS_REQUIRE(c && g && cam, "null argument struct");
-  GS_REQUIRE(0 <= first_gaussian && first_gaussian <= end_gaussian && end_gaussian <= g->num_gaussians, "bad gaussian range");
-  GS_REQUIRE(c->have_forward && c->rows_ready, "gsplat_backward_render has not run for this forward pass");
-  GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
-             "backward arguments do not match the recorded forward pass");
+static const gsplat_gradients kNoArrays = {};  // split form: the twelve common columns go to `common`, nothing else is stored
+
+// Everything the per-gaussian backward refuses, none of which needs a launch: a refused call leaves the caller's arrays
+// as they were (gsplat_backward_gaussians_adam asks before its SH kernel steps anything)
+static int check_backward_gaussians(const char *fn, const gsplat_context *c, const gsplat_gaussians *g,
+                                    const gsplat_camera *cam, int l_max, const gsplat_gradients *out, const float *common,
+                                    int first_gaussian, int end_gaussian, bool adam, int adam_mode, const float *grad_view,
+                                    const float *grad_campos) {
+  GS_REQUIRE_IN(fn, c && g && cam, "null argument struct");
+  GS_REQUIRE_IN(fn, 0 <= first_gaussian && first_gaussian <= end_gaussian && end_gaussian <= g->num_gaussians, "bad gaussian range");
+  GS_REQUIRE_IN(fn, c->have_forward && c->rows_ready, "gsplat_backward_render has not run for this forward pass");
+  if (int rc = check_recorded_forward(fn, c, g, cam, l_max)) return rc;
   const bool cam_grad = grad_view != nullptr;  // gsplat_backward_gaussians_camera: whole range, plain form
-  GS_REQUIRE(!(c->fwd_antialiased && adam),
-             "the forward ran in anti-aliased mode: the Adam-inside backward steps the opacity before the covariance chain "
-             "exists (use gsplat_backward_gaussians and the optimizer kernels)");
-  GS_REQUIRE(!(c->fwd_antialiased && cam_grad), "the forward ran in anti-aliased mode: the camera gradient has no such form");
+  GS_REQUIRE_IN(fn, !(c->fwd_antialiased && adam),
+                "the forward ran in anti-aliased mode: the Adam-inside backward steps the opacity before the covariance chain "
+                "exists (use gsplat_backward_gaussians and the optimizer kernels)");
+  GS_REQUIRE_IN(fn, !(c->fwd_antialiased && cam_grad), "the forward ran in anti-aliased mode: the camera gradient has no such form");
   if (cam_grad) {
-    GS_REQUIRE_DEV(grad_view); GS_REQUIRE_DEV(grad_campos);
-    GS_REQUIRE(!adam && !common && first_gaussian == 0 && end_gaussian == g->num_gaussians, "internal: camera form");
+    GS_REQUIRE_DEV_IN(fn, grad_view); GS_REQUIRE_DEV_IN(fn, grad_campos);
+    GS_REQUIRE_IN(fn, !adam && !common && first_gaussian == 0 && end_gaussian == g->num_gaussians, "internal: camera form");
   }
-  static const gsplat_gradients kNoArrays = {};
-  if (!out) out = &kNoArrays;  // split form: the twelve common columns go to `common`, nothing else is stored
+  if (!out) out = &kNoArrays;
   // (the Adam forms store only the arrays they are given; the camera form may be given none)
-  if (!common && !(adam && (out == &kNoArrays || adam_mode == 1)) && !(cam_grad && out == &kNoArrays)) {
-    GS_REQUIRE_DEV(out->grad_xyz); GS_REQUIRE_DEV(out->grad_rgb); GS_REQUIRE_DEV(out->grad_opacity);
-    GS_REQUIRE_DEV(out->grad_scale); GS_REQUIRE_DEV(out->grad_quaternion);
-    GS_REQUIRE(((uintptr_t)out->grad_quaternion & 15) == 0, "grad_quaternion must be 16-byte aligned");
-  }
-  if (l_max > 0 && out->grad_sh) GS_REQUIRE_DEV(out->grad_sh);  // NULL: the caller rebuilds them (gsplat_optimizer_step_sh_factored)
+  const bool leaves = !common && !(adam && (out == &kNoArrays || adam_mode == 1)) && !(cam_grad && out == &kNoArrays);
+  return check_gradient_arrays(fn, out, l_max, leaves);
+}
+
+static int backward_gaussians_impl(const char *fn, gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                                   int l_max, const gsplat_gradients *out, float *common, float *uv_norm, int first_gaussian,
+                                   int end_gaussian, void *stream, const AdamFused *adam = nullptr, int adam_mode = 2,
+                                   float *grad_view = nullptr, float *grad_campos = nullptr) {
+  int rc = check_backward_gaussians(fn, c, g, cam, l_max, out, common, first_gaussian, end_gaussian, adam != nullptr,
+                                    adam_mode, grad_view, grad_campos);
+  if (rc) return rc;
+  const bool cam_grad = grad_view != nullptr;
+  if (!out) out = &kNoArrays;
   hipStream_t st = (hipStream_t)stream;
   const int M = c->M, W = c->width, H = c->height;
-  // cuda/trainer.cu:992-995
   const float fx = cam->focal_x, fy = cam->focal_y;
-  const float fov_x = (float)(2.0 * atan((double)W / (2.0 * (double)fx)));
+  const float fov_x = (float)(2.0 * atan((double)W / (2.0 * (double)fx)));  // cuda/trainer.cu:992-995
   const float fov_y = (float)(2.0 * atan((double)H / (2.0 * (double)fy)));
   const float tan_fovx = tanf(fov_x * 0.5f), tan_fovy = tanf(fov_y * 0.5f);
   const float fwd_tan_fovx = c->tan_fovx, fwd_tan_fovy = c->tan_fovy;  // the recorded forward's (cuda/raster.cu:92-93)
@@ -2677,10 +2629,7 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
   const bool whole = first_gaussian == 0 && end_gaussian == g->num_gaussians;
   const int span = whole ? M : std::min(M, end_gaussian - first_gaussian);
   const int n_cam_rows = gs::div_up(span, 64);  // kCamGrad: one row of partial sums per wave
-  if (cam_grad && span > 0) {
-    const int rc = c->cam_rows.reserve((size_t)n_cam_rows * 16 * sizeof(double), st);
-    if (rc) return rc;
-  }
+  if (cam_grad && span > 0 && (rc = c->cam_rows.reserve((size_t)n_cam_rows * 16 * sizeof(double), st))) return rc;
   if (span == 0) {
     if (cam_grad) {  // nothing visible: the camera gradient is zero, not what the buffers held
       GS_HIP(hipMemsetAsync(grad_view, 0, 12 * sizeof(float), st));
@@ -2732,69 +2681,118 @@ static int backward_gaussians_impl(gsplat_context *c, const gsplat_gaussians *g,
   return GSPLAT_OK;
 }
 
-int gsplat_backward_pass(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
-                         const float *grad_image, float bg_color, int l_max, const gsplat_gradients *out,
-                         void *stream) {
-  GS_REQUIRE(c && g && cam && out, "null argument struct");
-  GS_REQUIRE(c->have_forward, "no forward pass recorded in this context");
-  GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
-             "backward arguments do not match the recorded forward pass");
-  GS_REQUIRE_DEV(out->grad_xyz); GS_REQUIRE_DEV(out->grad_rgb); GS_REQUIRE_DEV(out->grad_opacity);
-  GS_REQUIRE_DEV(out->grad_scale); GS_REQUIRE_DEV(out->grad_quaternion);
-  if (l_max > 0 && out->grad_sh) GS_REQUIRE_DEV(out->grad_sh);  // NULL: the caller rebuilds them (gsplat_optimizer_step_sh_factored)
-  int rc = gsplat_backward_render(c, grad_image, bg_color, nullptr, stream);
-  if (rc) return rc;
-  return gsplat_backward_gaussians(c, g, cam, l_max, out, stream);
+int gsplat_backward_gaussians(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
+                              const gsplat_gradients *out, void *stream) {
+  GS_REQUIRE(out != nullptr, "null argument struct");
+  return backward_gaussians_impl(__func__, c, g, cam, l_max, out, nullptr, nullptr, 0, g ? g->num_gaussians : 0, stream);
 }
 
-int gsplat_backward_pass_depth(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
-                               const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
-                               int l_max, const gsplat_gradients *out, void *stream) {
-  GS_REQUIRE(c && g && cam && out, "null argument struct");
-  GS_REQUIRE(c->have_forward, "no forward pass recorded in this context");
-  GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
-             "backward arguments do not match the recorded forward pass");
-  GS_REQUIRE_DEV(out->grad_xyz); GS_REQUIRE_DEV(out->grad_rgb); GS_REQUIRE_DEV(out->grad_opacity);
-  GS_REQUIRE_DEV(out->grad_scale); GS_REQUIRE_DEV(out->grad_quaternion);
-  GS_REQUIRE(((uintptr_t)out->grad_quaternion & 15) == 0, "grad_quaternion must be 16-byte aligned");
-  if (l_max > 0 && out->grad_sh) GS_REQUIRE_DEV(out->grad_sh);
-  int rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, nullptr, nullptr, nullptr, stream);
+int gsplat_backward_gaussians_range(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
+                                    const gsplat_gradients *out, int first_gaussian, int end_gaussian, void *stream) {
+  GS_REQUIRE(out != nullptr, "null argument struct");
+  return backward_gaussians_impl(__func__, c, g, cam, l_max, out, nullptr, nullptr, first_gaussian, end_gaussian, stream);
+}
+
+int gsplat_backward_gaussians_split(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
+                                    float *common, float *uv_norm, int first_gaussian, int end_gaussian, void *stream) {
+  GS_REQUIRE_DEV(common);
+  GS_REQUIRE(((uintptr_t)common & 15) == 0, "common must be 16-byte aligned");
+  if (uv_norm) GS_REQUIRE_DEV(uv_norm);
+  return backward_gaussians_impl(__func__, c, g, cam, l_max, nullptr, common, uv_norm, first_gaussian, end_gaussian, stream);
+}
+
+int gsplat_backward_gaussians_adam(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
+                                   const gsplat_adam_fused *opt, const gsplat_gradients *out, void *stream) {
+  GS_REQUIRE(opt != nullptr && g != nullptr, "null argument struct");
+  for (int k = 0; k < 6; ++k) {
+    if (k == 2 && l_max == 0) continue;  // no coefficients beyond band 0
+    GS_REQUIRE_DEV(opt->exp_avg[k]); GS_REQUIRE_DEV(opt->exp_avg_sq[k]);
+  }
+  GS_REQUIRE(((uintptr_t)opt->exp_avg[5] & 15) == 0 && ((uintptr_t)opt->exp_avg_sq[5] & 15) == 0,
+             "the quaternion moments must be 16-byte aligned");
+  if (opt->uv_grad_accum) GS_REQUIRE_DEV(opt->uv_grad_accum);
+  if (opt->grad_accum_dur) GS_REQUIRE_DEV(opt->grad_accum_dur);
+  AdamFused ad = {opt->exp_avg[0], opt->exp_avg_sq[0], opt->exp_avg[1], opt->exp_avg_sq[1], opt->exp_avg[2], opt->exp_avg_sq[2],
+                  opt->exp_avg[3], opt->exp_avg_sq[3], opt->exp_avg[4], opt->exp_avg_sq[4], opt->exp_avg[5], opt->exp_avg_sq[5],
+                  opt->lr[0], opt->lr[1], opt->lr[2], opt->lr[3], opt->lr[4], opt->lr[5],
+                  opt->b1, opt->b2, opt->eps, opt->bias1, opt->bias2, opt->uv_grad_accum, opt->grad_accum_dur, nullptr};
+  GS_REQUIRE(opt->mode >= 0 && opt->mode <= 2,
+             "mode: 0 all six groups in one kernel, 1 SH and position left to the optimizer kernels, 2 the SH group in a kernel of its own in front");
+  if (opt->mode == 1) {
+    GS_REQUIRE(out != nullptr, "mode 1 hands grad_xyz and grad_precompute_rgb to the optimizer kernels: `out` is needed");
+    GS_REQUIRE_DEV(out->grad_xyz);
+    if (l_max > 0) GS_REQUIRE_DEV(out->grad_precompute_rgb);
+  }
+  const int adam_mode = opt->mode == 1 ? 1 : opt->mode == 2 ? 3 : 2;
+  // everything the per-gaussian backward below could refuse, BEFORE sh_adam_dir_kernel steps the SH group in place
+  int rc = check_backward_gaussians(__func__, c, g, cam, l_max, out, nullptr, 0, g->num_gaussians, true, adam_mode, nullptr, nullptr);
   if (rc) return rc;
-  return gsplat_backward_gaussians(c, g, cam, l_max, out, stream);
+  if (opt->mode == 2 && l_max > 0 && c->M > 0) {
+    // the SH rows are read ONCE, by sh_adam_dir_kernel: their Adam step and sh_bwd's sums over them; the per-gaussian
+    // backward behind it (kAdam 3) takes the position gradient through the view direction from c->dir_grad
+    hipStream_t st = (hipStream_t)stream;
+    if ((rc = c->dir_grad.reserve((size_t)c->M * 3 * sizeof(float), st))) return rc;
+    ad.dir = c->dir_grad.as<float>();
+    const unsigned int blocks = (unsigned int)(((long long)c->M * 16 + kBlock - 1) / kBlock);
+    float *sh_p = const_cast<float *>(g->sh);
+#define GS_SHA(LL)                                                                                                     \
+  sh_adam_dir_kernel<LL><<<blocks, kBlock, 0, st>>>(c->M, c->c2g.as<int>(), sh_p, ad.m_sh, ad.v_sh, ad.lr_sh, ad.b1, ad.b2,  \
+                                                   ad.eps, ad.bias1, ad.bias2, g->xyz, g->rgb, cam->campos[0], cam->campos[1], \
+                                                   cam->campos[2], c->grad_rows.as<float4>(), ad.dir)
+    switch (l_max) {
+      case 1: GS_SHA(1); break;
+      case 2: GS_SHA(2); break;
+      default: GS_SHA(3); break;
+    }
+#undef GS_SHA
+    GS_LAUNCH_CHECK();
+  }
+  return backward_gaussians_impl(__func__, c, g, cam, l_max, out, nullptr, nullptr, 0, g->num_gaussians, stream, &ad, adam_mode);
 }
 
 int gsplat_backward_gaussians_camera(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, int l_max,
                                      const gsplat_gradients *out, float *grad_view, float *grad_campos, void *stream) {
   GS_REQUIRE_DEV(grad_view); GS_REQUIRE_DEV(grad_campos);
-  return backward_gaussians_impl(c, g, cam, l_max, out, nullptr, nullptr, 0, g ? g->num_gaussians : 0, stream, nullptr, 2,
+  return backward_gaussians_impl(__func__, c, g, cam, l_max, out, nullptr, nullptr, 0, g ? g->num_gaussians : 0, stream,
+                                 nullptr, 2, grad_view, grad_campos);
+}
+
+// gsplat_backward_pass*: every check of the two halves before the first launch, then the halves.  `camera`: the form
+// that also returns the pose gradient and may be given no `out`.
+static int backward_pass(const char *fn, gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                         const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
+                         int l_max, const gsplat_gradients *out, bool camera, float *grad_view, float *grad_campos,
+                         void *stream) {
+  GS_REQUIRE_IN(fn, c && g && cam && (out || camera), "null argument struct");
+  int rc = check_recorded_forward(fn, c, g, cam, l_max);
+  if (rc) return rc;
+  if (camera) {
+    GS_REQUIRE_DEV_IN(fn, grad_view); GS_REQUIRE_DEV_IN(fn, grad_campos);
+    GS_REQUIRE_IN(fn, !c->fwd_antialiased, "the forward ran in anti-aliased mode: the camera gradient has no such form");
+  }
+  if (out && (rc = check_gradient_arrays(fn, out, l_max))) return rc;
+  // (the compositing half checks its own arguments before its first launch)
+  rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, nullptr, nullptr, nullptr, stream);
+  if (rc) return rc;
+  return backward_gaussians_impl(fn, c, g, cam, l_max, out, nullptr, nullptr, 0, g->num_gaussians, stream, nullptr, 2,
                                  grad_view, grad_campos);
+}
+
+int gsplat_backward_pass(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam, const float *grad_image,
+                         float bg_color, int l_max, const gsplat_gradients *out, void *stream) {  // (the depth form with two null maps: the plain backward, exactly)
+  return backward_pass(__func__, c, g, cam, grad_image, nullptr, nullptr, bg_color, l_max, out, false, nullptr, nullptr, stream);
+}
+
+int gsplat_backward_pass_depth(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                               const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
+                               int l_max, const gsplat_gradients *out, void *stream) {
+  return backward_pass(__func__, c, g, cam, grad_image, grad_depth, grad_alpha, bg_color, l_max, out, false, nullptr, nullptr, stream);
 }
 
 int gsplat_backward_pass_camera(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
                                 const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
-                                int l_max, const gsplat_gradients *out, float *grad_view, float *grad_campos,
-                                void *stream) {
-  // every check of the two calls below before the first launch
-  GS_REQUIRE(c && g && cam, "null argument struct");
-  GS_REQUIRE(c->have_forward, "no forward pass recorded in this context");
-  GS_REQUIRE(l_max == c->l_max && g->num_gaussians == c->N && cam->width == c->width && cam->height == c->height,
-             "backward arguments do not match the recorded forward pass");
-  GS_REQUIRE_DEV(grad_view); GS_REQUIRE_DEV(grad_campos);
-  GS_REQUIRE(!c->fwd_antialiased, "the forward ran in anti-aliased mode: the camera gradient has no such form");
-  if (out) {
-    GS_REQUIRE_DEV(out->grad_xyz); GS_REQUIRE_DEV(out->grad_rgb); GS_REQUIRE_DEV(out->grad_opacity);
-    GS_REQUIRE_DEV(out->grad_scale); GS_REQUIRE_DEV(out->grad_quaternion);
-    GS_REQUIRE(((uintptr_t)out->grad_quaternion & 15) == 0, "grad_quaternion must be 16-byte aligned");
-    if (l_max > 0 && out->grad_sh) GS_REQUIRE_DEV(out->grad_sh);
-  }
-  GS_REQUIRE_DEV(grad_image);
-  if (grad_depth) GS_REQUIRE_DEV(grad_depth);
-  if (grad_alpha) GS_REQUIRE_DEV(grad_alpha);
-  GS_REQUIRE(!(grad_depth || grad_alpha) || c->depth_ready,
-             "depth / alpha gradients need a forward that rendered depth (gsplat_context_set_depth)");
-  int rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, nullptr, nullptr, nullptr, stream);
-  if (rc) return rc;
-  return gsplat_backward_gaussians_camera(c, g, cam, l_max, out, grad_view, grad_campos, stream);
+                                int l_max, const gsplat_gradients *out, float *grad_view, float *grad_campos, void *stream) {
+  return backward_pass(__func__, c, g, cam, grad_image, grad_depth, grad_alpha, bg_color, l_max, out, true, grad_view, grad_campos, stream);
 }
 
 int gsplat_context_set_depth(gsplat_context *c, int enabled) {
@@ -2880,8 +2878,8 @@ int gsplat_context_set_timing_stages(gsplat_context *c, unsigned int stage_mask)
 
 int gsplat_context_get_counters(gsplat_context *c, long long *out, int n) {
   GS_REQUIRE(c && out && n >= 0, "null argument");
-  // (reporting only: the freshest pair of figures either slot holds -- the forward's decisions use queue_tail's rule)
-  long long fmax = c->fig_max, fsum = c->fig_sum;
+  // (reporting only: the freshest pair of figures either slot holds -- the forward's decisions use gs::take_figures)
+  long long fmax = c->fig.max, fsum = c->fig.sum;
   unsigned int best = 0;
   for (int sl = 0; sl < 2; ++sl) {
     const unsigned long long w0 = __atomic_load_n(&c->h_pub[8 + 4 * sl], __ATOMIC_RELAXED);

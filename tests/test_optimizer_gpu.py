@@ -220,6 +220,43 @@ def test_backward_with_adam_inside_equals_backward_then_optimizer(gpu, scene, na
         assert not torch.equal(dp_b[g], before[g]), g
 
 
+def test_refused_adam_backward_steps_nothing(gpu, scene):
+    """gsplat_backward_gaussians_adam, mode 2, runs sh_adam_dir_kernel -- the SH group's Adam step, in place -- in front of
+    the per-gaussian backward.  A call that the backward refuses (here: a camera 16 pixels wider than the recorded
+    forward's) must be refused BEFORE that kernel: the SH rows and both of their moments stay bit for bit what they were,
+    and the same call with the right camera then succeeds and steps them."""
+    torch, raster, opt_mod = gpu, pkg("raster"), pkg("optimizer")
+    GsplatError = pkg("_lib").GsplatError
+    N, W, H, L = 3000, 160, 96, 1  # small_l1: the smallest shape at which mode 2's SH kernel runs at all
+    params = scene.make_gaussians(N, W, H, L)
+    params["xyz"][::3, 2] *= -1
+    cam = scene.make_camera(W, H, 1)
+    c = scene.CONFIG
+    ctx = raster.RasterContext(N, W, H)
+    dp, dc = raster.device_params(params), raster.device_camera(cam)
+    opt = opt_mod.AdamOptimizer(dp, L, scene_extent=2.5)
+    rng = np.random.default_rng(7)
+    opt.exp_avg["sh"].copy_(torch.from_numpy((rng.standard_normal(tuple(opt.exp_avg["sh"].shape)) * 1e-4).astype(np.float32)))
+    opt.exp_avg_sq["sh"].copy_(torch.from_numpy((rng.random(tuple(opt.exp_avg_sq["sh"].shape)) * 1e-8).astype(np.float32)))
+    fwd = ctx.rasterize_image(dp, dc, c, c["bg"], L)
+    assert 0 < fwd["num_culled"] < N
+    ctx.backward_render(torch.as_tensor(scene.make_grad_image(W, H)).cuda(), c["bg"])
+    torch.cuda.synchronize()
+    sh, m, v = dp["sh"].clone(), opt.exp_avg["sh"].clone(), opt.exp_avg_sq["sh"].clone()
+    wider = dict(dc)
+    wider["width"] = W + 16
+    it = 20
+    with pytest.raises(GsplatError) as refused:
+        ctx.backward_gaussians_adam(dp, wider, L, opt.fused_state(it, mode=2), None)
+    assert refused.value.code == -3
+    torch.cuda.synchronize()
+    assert torch.equal(dp["sh"], sh), "a refused call moved SH rows"
+    assert torch.equal(opt.exp_avg["sh"], m) and torch.equal(opt.exp_avg_sq["sh"], v), "a refused call moved SH moments"
+    ctx.backward_gaussians_adam(dp, dc, L, opt.fused_state(it, mode=2), None)
+    torch.cuda.synchronize()
+    assert not torch.equal(dp["sh"], sh) and not torch.equal(opt.exp_avg["sh"], m)
+
+
 def test_training_iterations_reduce_the_loss(gpu, scene):
     """rasterize -> fused_loss -> backward -> optimizer step, 30 iterations on one view toward a target rendered
     from the unperturbed scene: the L1+SSIM loss must drop and PSNR must rise (reference loop: trainer.cu:417-516)."""
