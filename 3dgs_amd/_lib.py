@@ -220,6 +220,10 @@ SIGNATURES = {
     "gsplat_context_set_antialiased": (_I, [_P, _I]),
     "gsplat_compute_conic_antialiased": (_I, [_P, _P, _P, _F, _F, _F, _F, _F, _I, _P, _P, _P, _P, _P]),
     "gsplat_compute_conic_antialiased_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "gsplat_compute_filter3d": (_I, [_P, _I, _P, _P, _P, _P, _I, _F, _P, _P]),
+    "gsplat_filter3d_apply": (_I, [_P, _P, _P, _I, _P, _P, _P]),
+    "gsplat_filter3d_apply_backward": (_I, [_P, _P, _P, _P, _I, _P, _I, _P, _I, _P]),
+    "gsplat_context_set_filter3d": (_I, [_P, _P]),
     "gsplat_context_set_preprocess_split": (_I, [_P, _I]),
     "gsplat_context_get_counters": (_I, [_P, ctypes.POINTER(ctypes.c_longlong), _I]),
     "gsplat_context_set_timing": (_I, [_P, _I]),

@@ -61,6 +61,12 @@ int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorte
 int launch_tile_segments(const int *ranges, const int *tops, int num_tiles, const TileSegments &seg, hipStream_t st);
 int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
 bool tile_order_supported(int num_tiles);
+// gs_filter3d.hip: the 3D smoothing filter's parameter transform and its chain rule (gsplat_context_set_filter3d)
+int launch_filter3d_apply(const float *scale, const float *opacity, const float *filter3d, int N, float *scale_eff,
+                          float *opacity_eff, hipStream_t st);
+int launch_filter3d_apply_bwd(const float *scale, const float *opacity, const float *filter3d, const int *rows, int M,
+                              float *grad_scale, int scale_stride, float *grad_opacity, int opacity_stride,
+                              bool at_gaussian, int first, int end, int span, hipStream_t st);
 }  // namespace gs
 
 // GSPLAT_PRE_SPLIT=0|1|2: the per-gaussian forward as one kernel (the default), as sh_colour_kernel + preprocess_geom_kernel
@@ -111,6 +117,13 @@ struct gsplat_context {
   // row slot 3 into dL/d logit and the covariance term of dL/d rho
   bool antialiased = false;
   bool fwd_antialiased = false;  // the recorded forward ran in the mode (its backwards follow it, whatever is set by then)
+  // 3D smoothing filter (gsplat_context_set_filter3d; gs_filter3d.hip): the forward runs on scale_eff / opacity_eff, which
+  // it writes into f3d_scale [max_gaussians,3] / f3d_opacity [max_gaussians] first (allocated by the first forward in the
+  // mode); the per-gaussian backwards of that forward recompute from the same two arrays and then apply the chain rule to
+  // the scale and opacity gradients they have stored
+  const float *filter3d = nullptr;      // caller-owned [N], global order; read by the next forward
+  const float *fwd_filter3d = nullptr;  // what the recorded forward ran with (its backwards follow it)
+  gs::DeviceBuffer f3d_scale, f3d_opacity;
   void *fseg_gran_zeroed = nullptr;  // the granule block whose tags have been cleared (a fresh block holds anything)
   size_t fseg_gran_zeroed_bytes = 0;
   unsigned int fseg_epoch = 0;
@@ -192,7 +205,7 @@ struct gsplat_context {
                                      &rgb, &radius, &recs, &counts, &offsets, &grad_rows, &hitmask, &keys_a, &keys_b, &pay_a, &pay_b,
                                      &sorted, &temp, &ranges, &image, &T_px, &n_px, &blockmasks, &kept, &tile_tops, &tile_order,
                                      &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad, &cam_rows,
-                                     &depth_map, &seg_chk_d, &fseg_part_d};
+                                     &depth_map, &seg_chk_d, &fseg_part_d, &f3d_scale, &f3d_opacity};
     size_t b = 0;
     for (auto *p : all) b += p->bytes;
     return b;
@@ -204,7 +217,7 @@ struct gsplat_context {
                                &rgb, &radius, &recs, &counts, &offsets, &grad_rows, &hitmask, &keys_a, &keys_b, &pay_a, &pay_b,
                                &sorted, &temp, &bin_table, &ranges, &image, &T_px, &n_px, &blockmasks, &kept, &tile_tops, &tile_order,
                                &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad, &cam_rows,
-                               &depth_map, &seg_chk_d, &fseg_part_d};
+                               &depth_map, &seg_chk_d, &fseg_part_d, &f3d_scale, &f3d_opacity};
     for (auto *p : all) p->release();
     fseg_gran_zeroed = nullptr;
     fork.destroy();
@@ -2423,6 +2436,18 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   if ((rc = reclaim_outputs(c, st))) return rc;
+  // 3D smoothing filter: the chain below runs, unchanged, on the filtered scale and opacity
+  gsplat_gaussians filtered;
+  if (c->filter3d) {
+    GS_REQUIRE_DEV(c->filter3d);
+    if ((rc = c->f3d_scale.reserve((size_t)c->max_gaussians * 3 * sizeof(float), st))) return rc;
+    if ((rc = c->f3d_opacity.reserve((size_t)c->max_gaussians * sizeof(float), st))) return rc;
+    if ((rc = gs::launch_filter3d_apply(g->scale, g->opacity, c->filter3d, g->num_gaussians, c->f3d_scale.as<float>(),
+                                        c->f3d_opacity.as<float>(), st))) return rc;
+    filtered = *g; filtered.scale = c->f3d_scale.as<float>(); filtered.opacity = c->f3d_opacity.as<float>();
+    g = &filtered;
+  }
+  c->fwd_filter3d = c->filter3d;
   FwdCall f;
   if ((rc = plan_forward_call(c, g, cam, cfg, bg_color, l_max, st, f))) return rc;
   if (c->timing) {  // next timing slot; its events are >= kSlots forwards old, hence complete
@@ -2595,6 +2620,9 @@ static int check_backward_gaussians(const char *fn, const gsplat_context *c, con
                 "the forward ran in anti-aliased mode: the Adam-inside backward steps the opacity before the covariance chain "
                 "exists (use gsplat_backward_gaussians and the optimizer kernels)");
   GS_REQUIRE_IN(fn, !(c->fwd_antialiased && cam_grad), "the forward ran in anti-aliased mode: the camera gradient has no such form");
+  GS_REQUIRE_IN(fn, !(c->fwd_filter3d && adam),
+                "the forward ran with a 3D smoothing filter: the Adam-inside backward would step the filtered scale and "
+                "opacity it differentiates (use gsplat_backward_gaussians and the optimizer kernels)");
   if (cam_grad) {
     GS_REQUIRE_DEV_IN(fn, grad_view); GS_REQUIRE_DEV_IN(fn, grad_campos);
     GS_REQUIRE_IN(fn, !adam && !common && first_gaussian == 0 && end_gaussian == g->num_gaussians, "internal: camera form");
@@ -2615,6 +2643,14 @@ static int backward_gaussians_impl(const char *fn, gsplat_context *c, const gspl
   const bool cam_grad = grad_view != nullptr;
   if (!out) out = &kNoArrays;
   hipStream_t st = (hipStream_t)stream;
+  // 3D smoothing filter: the kernel recomputes from what the forward ran on -- the filtered scale and opacity, still in
+  // the workspace -- and the chain rule to the raw ones follows it (below)
+  const float *raw_scale = g->scale, *raw_opacity = g->opacity;
+  gsplat_gaussians filtered;
+  if (c->fwd_filter3d) {
+    filtered = *g; filtered.scale = c->f3d_scale.as<float>(); filtered.opacity = c->f3d_opacity.as<float>();
+    g = &filtered;
+  }
   const int M = c->M, W = c->width, H = c->height;
   const float fx = cam->focal_x, fy = cam->focal_y;
   const float fov_x = (float)(2.0 * atan((double)W / (2.0 * (double)fx)));  // cuda/trainer.cu:992-995
@@ -2676,6 +2712,16 @@ static int backward_gaussians_impl(const char *fn, gsplat_context *c, const gspl
   if (cam_grad) {
     cam_grad_finalize_kernel<<<1, kCamFinThreads, 0, st>>>(c->cam_rows.as<double>(), n_cam_rows, grad_view, grad_campos);
     GS_LAUNCH_CHECK();
+  }
+  if (c->fwd_filter3d) {  // d/d (scale_eff, opacity_eff) -> d/d (scale, opacity), in place on the rows just written
+    const int lo = whole ? 0 : first_gaussian, hi = whole ? 0 : end_gaussian;
+    if (common)
+      rc = gs::launch_filter3d_apply_bwd(raw_scale, raw_opacity, c->fwd_filter3d, c->c2g.as<int>(), M, common + 4, 12,
+                                         common + 3, 12, true, lo, hi, span, st);
+    else if (out->grad_scale && out->grad_opacity)
+      rc = gs::launch_filter3d_apply_bwd(raw_scale, raw_opacity, c->fwd_filter3d, c->c2g.as<int>(), M, out->grad_scale, 3,
+                                         out->grad_opacity, 1, false, lo, hi, span, st);
+    if (rc) return rc;
   }
   c->mark(7, true, st);
   return GSPLAT_OK;
@@ -2804,6 +2850,13 @@ int gsplat_context_set_depth(gsplat_context *c, int enabled) {
 int gsplat_context_set_antialiased(gsplat_context *c, int enabled) {
   GS_REQUIRE(c != nullptr, "null context");
   c->antialiased = enabled != 0;  // (read by the next forward; a backward follows the forward it belongs to)
+  return GSPLAT_OK;
+}
+
+int gsplat_context_set_filter3d(gsplat_context *c, const float *filter3d) {
+  GS_REQUIRE(c != nullptr, "null context");
+  if (filter3d) GS_REQUIRE_DEV(filter3d);
+  c->filter3d = filter3d;  // (read by the next forward; a backward follows the forward it belongs to)
   return GSPLAT_OK;
 }
 

@@ -257,3 +257,66 @@ def compact_masked_array(stride, d_source, d_mask, num_culled=None):
 def scatter_masked_array(stride, d_compacted, d_mask, d_destination):
     check(_lib.load().gsplat_scatter_masked_array(_p(d_compacted), _p(d_mask), int(d_mask.numel()), stride,
                                                   _p(d_destination), _stream()))
+
+
+def camera_arrays(cams, device="cuda"):
+    """The device camera arrays compute_filter3d reads, from a list of camera dicts (scene.make_camera /
+    raster.device_camera): views [V,16], projs [V,16], focal_x [V] float32 and sizes [V,2] int32 (width, height)."""
+    import numpy as np
+
+    def host(m):
+        return (m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)).astype(np.float32).reshape(16)
+
+    views = torch.as_tensor(np.stack([host(c["view"]) for c in cams])).to(device).contiguous()
+    projs = torch.as_tensor(np.stack([host(c["proj"]) for c in cams])).to(device).contiguous()
+    focal = torch.as_tensor(np.asarray([float(c["fx"]) for c in cams], np.float32)).to(device)
+    sizes = torch.as_tensor(np.asarray([[int(c["width"]), int(c["height"])] for c in cams], np.int32)).to(device)
+    return views, projs, focal, sizes.contiguous()
+
+
+def compute_filter3d(xyz, views, projs, focal_x, sizes, near=0.2, out=None):
+    """The 3D smoothing filter of every gaussian (gsplat_compute_filter3d): filter3d[i] = sqrt(0.2) * the smallest
+    z / focal_x over the cameras that sample gaussian i; a gaussian no camera samples takes the largest value of the
+    sampled ones.  Camera arrays as camera_arrays() returns them.  Returns the [N] float32 device tensor."""
+    N, V = int(xyz.shape[0]), int(focal_x.shape[0])
+    if views.numel() != 16 * V or projs.numel() != 16 * V or sizes.numel() != 2 * V or sizes.dtype != torch.int32:
+        raise ValueError("views / projs must be [V,16] float32, sizes [V,2] int32")
+    if out is None:
+        out = torch.empty(N, dtype=torch.float32, device=xyz.device)
+    check(_lib.load().gsplat_compute_filter3d(_p(_f32(xyz, "xyz")), N, _p(_f32(views, "views")), _p(_f32(projs, "projs")),
+                                              _p(_f32(focal_x, "focal_x")), _p(sizes), V, float(near),
+                                              _p(_f32(out, "out")), _stream()))
+    return out
+
+
+def filter3d_apply(scale, opacity, filter3d, scale_eff=None, opacity_eff=None):
+    """(scale [N,3], opacity [N], filter3d [N]) -> (scale_eff, opacity_eff): the parameters a filtered gaussian enters the
+    rasterizer with (gsplat_filter3d_apply); rows with filter3d == 0 come back bit-identical."""
+    N = int(opacity.shape[0])
+    scale_eff = torch.empty_like(scale) if scale_eff is None else scale_eff
+    opacity_eff = torch.empty_like(opacity) if opacity_eff is None else opacity_eff
+    check(_lib.load().gsplat_filter3d_apply(_p(_f32(scale, "scale")), _p(_f32(opacity, "opacity")),
+                                            _p(_f32(filter3d, "filter3d")), N, _p(_f32(scale_eff, "scale_eff")),
+                                            _p(_f32(opacity_eff, "opacity_eff")), _stream()))
+    return scale_eff, opacity_eff
+
+
+def filter3d_apply_backward(scale, opacity, filter3d, grad_scale, grad_opacity, rows=None):
+    """The filter's chain rule, in place (gsplat_filter3d_apply_backward): grad_scale [M,3] / grad_opacity [M] hold the
+    gradients with respect to scale_eff / opacity_eff and leave as those with respect to scale / opacity.  Gradient row j
+    belongs to gaussian rows[j] (int32 device tensor; None: j).  The two gradient tensors may be column views of a wider
+    row-major buffer (common[:, 4:7], common[:, 3]): only their rows' stride has to be uniform."""
+    M = int(grad_opacity.shape[0])
+    if grad_scale.dim() != 2 or grad_scale.shape[1] != 3 or grad_scale.shape[0] != M or grad_opacity.dim() != 1:
+        raise ValueError("grad_scale must be [M,3] and grad_opacity [M]")
+    if M > 1 and grad_scale.stride(1) != 1:
+        raise ValueError("the three scale gradients of a row must be adjacent")
+    if rows is not None and (rows.dtype != torch.int32 or rows.numel() != M):
+        raise ValueError("rows must be an int32 tensor with one entry per gradient row")
+    _f32(grad_scale, "grad_scale"), _f32(grad_opacity, "grad_opacity")
+    if M == 0:
+        return
+    check(_lib.load().gsplat_filter3d_apply_backward(
+        _p(_f32(scale, "scale")), _p(_f32(opacity, "opacity")), _p(_f32(filter3d, "filter3d")), _p(rows), M,
+        ctypes.c_void_p(grad_scale.data_ptr()), int(grad_scale.stride(0)) if M > 1 else 3,
+        ctypes.c_void_p(grad_opacity.data_ptr()), int(grad_opacity.stride(0)) if M > 1 else 1, _stream()))

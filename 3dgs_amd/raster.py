@@ -126,6 +126,7 @@ class RasterContext:
         self._h = h
         self._last = None
         self._depth = False
+        self._filter3d = self._filter3d_fwd = None
         self.max_gaussians, self.max_width, self.max_height = int(max_gaussians), int(max_width), int(max_height)
 
     def close(self):
@@ -184,6 +185,19 @@ class RasterContext:
         of the projected covariance -- and backward_pass / backward_gaussians (whole, range, split) return the gradients
         of that image.  The Adam-inside and camera backwards and the two-kernel forward refuse the mode."""
         check(self._lib.gsplat_context_set_antialiased(self._h, int(bool(enabled))))
+
+    def set_filter3d(self, filter3d):
+        """3D smoothing filter (gsplat_context_set_filter3d): filter3d is the [N] float32 device tensor of
+        ops.compute_filter3d, in global gaussian order, or None to switch the mode off.  From the next forward on every
+        gaussian is rasterized with the scale and opacity of ops.filter3d_apply, and backward_pass / backward_gaussians
+        (whole, range, split, camera) return the gradients with respect to the RAW scale and opacity.  The Adam-inside
+        backwards refuse the mode.  The context keeps the tensor alive for as long as a forward or backward may read it."""
+        if filter3d is not None:
+            if (not isinstance(filter3d, torch.Tensor) or filter3d.dtype != torch.float32 or not filter3d.is_cuda
+                    or not filter3d.is_contiguous() or filter3d.dim() != 1):
+                raise ValueError("filter3d must be a contiguous [N] float32 device tensor or None")
+        check(self._lib.gsplat_context_set_filter3d(self._h, _ptr(filter3d)))
+        self._filter3d = filter3d if filter3d is not None and filter3d.numel() else None
 
     def absgrad_uv(self):
         """abs_uv [M,2] of the last compositing backward (compacted order): (sum_p |du_p|, sum_p |dv_p|) over the pixels'
@@ -246,6 +260,9 @@ class RasterContext:
         """params: dict of device tensors (xyz rgb sh opacity scale quaternion); sh must be stored with the
         current band's stride, [N,(l_max+1)^2-1,3] (cuda_data.cuh layout).  Returns a dict of views."""
         g, c = self._structs(params, cam, l_max)
+        if self._filter3d is not None and self._filter3d.numel() != g.num_gaussians:
+            raise ValueError("the 3D filter has %d rows for %d gaussians" % (self._filter3d.numel(), g.num_gaussians))
+        self._filter3d_fwd = self._filter3d  # the backwards of this forward read the same array
         if l_max > 0:
             want = ((l_max + 1) ** 2 - 1) * 3
             if params["sh"].numel() != g.num_gaussians * want:

@@ -34,7 +34,13 @@ DEFAULT_CONFIG = dict(
     # antialiased: every gaussian composites with sigmoid(opacity) * rho, the opacity compensation for the 0.3 px blur of
     # its projected covariance (RasterContext.set_antialiased), in training and in evaluate(); the optimizer step then
     # runs behind the backward (the GSPLAT_FUSED_ADAM=0 choreography), which has no Adam-inside form in the mode
-    antialiased=False)
+    antialiased=False,
+    # filter3d: the 3D smoothing filter, the other half of Mip-Splatting (RasterContext.set_filter3d): every gaussian is
+    # rasterized as Sigma + f^2 I with its opacity scaled by sqrt(det Sigma / det(Sigma + f^2 I)), f = sqrt(0.2) * the
+    # smallest depth / focal length over the training views that see it (closer than filter3d_near: not seen), in
+    # training and in evaluate().  f is recomputed every filter3d_interval iterations and whenever the gaussian set or
+    # its order changes; the optimizer step runs behind the backward, as with antialiased
+    filter3d=False, filter3d_interval=100, filter3d_near=0.2)
 
 
 def _logit(p):
@@ -81,8 +87,10 @@ class Trainer:
         #   2: all six groups inside the backward (one fat kernel at three waves per SIMD: 356 us, 2 % slower);
         #   0: the backward stores its gradients, the two optimizer kernels read them (r01-r05).
         self.fused_adam = int(__import__("os").environ.get("GSPLAT_FUSED_ADAM", "1") or 0)
-        if self.cfg["antialiased"]:
-            self.fused_adam = 0  # whatever the environment says: the Adam-inside backward refuses the mode
+        if self.cfg["antialiased"] or self.cfg["filter3d"]:
+            self.fused_adam = 0  # whatever the environment says: the Adam-inside backward refuses the modes
+        self._filter3d = None       # [N] device tensor of the current gaussians; None: to be (re)computed
+        self._filter3d_cams = None  # the training views' device camera arrays, built once
         self._sharded = None  # (key, ViewShardedStep) for the current gaussian count / SH degree
         self._grad_image = {}  # (H, W) -> dL/dimage buffer, allocated once per image size
         self._grads = None     # (capacity, l_max, dict): per-view gradient arrays, reused across iterations
@@ -105,6 +113,7 @@ class Trainer:
         self.ctx_capacity = n
         self._new_optimizer(None)
         self.history = []
+        self._set_filter3d(self.ctx)
 
     # ------------------------------------------------------------------ state
     @property
@@ -114,6 +123,7 @@ class Trainer:
     def _new_optimizer(self, moments):
         """Fresh AdamOptimizer over the current parameter tensors; `moments` = (exp_avg, exp_avg_sq) dicts to adopt."""
         self._sharded = None  # the parameter tensors were replaced: the exchange step binds to the new ones
+        self._filter3d = None  # ... and the gaussian set or its order changed (density control, Morton re-order)
         p = dict(self.params)
         if self.l_max == 0:
             p.pop("sh")
@@ -130,7 +140,29 @@ class Trainer:
             self.ctx.set_lean_forward(True)
             self.ctx.set_absgrad(bool(self.cfg["absgrad"]))
             self.ctx.set_antialiased(bool(self.cfg["antialiased"]))
+        self._set_filter3d(self.ctx)
         return self.ctx
+
+    @property
+    def filter3d(self):
+        """The 3D smoothing filter of the current gaussians ([N] device tensor; None when the config key is off),
+        computed from all training views (ops.compute_filter3d) when positions, set or order have changed since."""
+        if not self.cfg["filter3d"] or self.num_gaussians == 0:
+            return None
+        if self._filter3d is None:
+            if self._filter3d_cams is None:
+                self._filter3d_cams = ops.camera_arrays([c for c, _ in self.views], self.params["xyz"].device)
+            self._filter3d = ops.compute_filter3d(self.params["xyz"], *self._filter3d_cams,
+                                                  near=float(self.cfg["filter3d_near"]))
+        return self._filter3d
+
+    def _set_filter3d(self, ctx):
+        if self.cfg["filter3d"] and ctx._filter3d is not self.filter3d:
+            ctx.set_filter3d(self.filter3d)
+
+    def _refresh_filter3d(self, it):
+        if self.cfg["filter3d"] and it % int(self.cfg["filter3d_interval"]) == 0 and it > 0:
+            self._filter3d = None  # the positions have moved
 
     # ------------------------------------------------------------------ one iteration (cuda/trainer.cu:1338-1362)
     def _grad_image_for(self, H, W, device):
@@ -166,6 +198,7 @@ class Trainer:
         bg = (it % 255) / 255.0 if c["use_background"] else 0.0
         if it % c["add_sh_band_interval"] == 0 and it >= c["add_sh_band_interval"]:
             self.add_sh_band()
+        self._refresh_filter3d(it)
         ctx = self._context_for(self.num_gaussians)
         p = dict(self.params)
         H, W = int(cam["height"]), int(cam["width"])
@@ -179,7 +212,7 @@ class Trainer:
         grad_image = self._grad_image_for(H, W, gt_image.device)
         # the loss value is a blocking read-back: only fetched when the caller logs it
         loss = ops.fused_loss(fwd["image"], gt_image, H, W, float(c["ssim_frac"]), grad_image, blocking=want_loss)
-        fused_adam = 0 if c["antialiased"] else self.fused_adam
+        fused_adam = 0 if c["antialiased"] or c["filter3d"] else self.fused_adam
         if fused_adam == 3:
             # r06: the SH group's step in a kernel that reads the coefficient rows once (update + the sums the position
             # gradient needs), then the per-gaussian backward with the five small groups' steps inside: no gradient arrays
@@ -208,8 +241,10 @@ class Trainer:
         bg = (it % 255) / 255.0 if c["use_background"] else 0.0
         if it % c["add_sh_band_interval"] == 0 and it >= c["add_sh_band_interval"]:
             self.add_sh_band()
+        self._refresh_filter3d(it)
         n = self.num_gaussians
         key = (n, self.l_max)
+        self._context_for(n)  # (the step below runs on this context, with the current 3D filter set)
         if self._sharded is None or self._sharded[0] != key:
             ctx = self._context_for(n)
             p = dict(self.params)
@@ -272,7 +307,7 @@ class Trainer:
 
     def evaluate(self, views=None):
         """Mean PSNR over the views at background 0 (TrainerImpl::evaluate, cuda/trainer.cu:263-360), rendered in the
-        mode the run trains in (config key antialiased)."""
+        mode the run trains in (config keys antialiased, filter3d)."""
         total, views = 0.0, (views or self.views)
         ctx = self._context_for(self.num_gaussians)
         ctx.set_render_only(True)  # nothing here runs a backward
@@ -400,13 +435,18 @@ class Trainer:
         self.opt.uv_grad_accum = ops.gather_rows(acc[0], order)
         self.opt.grad_accum_dur = ops.gather_rows(acc[1].view(torch.float32), order).view(torch.int32)
 
-    def save_to_ply(self, path):
-        """TrainerImpl::save_to_ply (cuda/trainer.cu:1166-1196): the device quaternion (kernel order w,x,y,z) is
+    def save_to_ply(self, path, raw=False):
+        """With the 3D smoothing filter on, the file holds the FUSED scale and opacity (ops.filter3d_apply: what the run
+        rasterizes), so that an ordinary viewer shows what was trained; raw=True writes the raw parameters.
+        TrainerImpl::save_to_ply (cuda/trainer.cu:1166-1196): the device quaternion (kernel order w,x,y,z) is
         memcpy'd into Eigen's (x,y,z,w) storage and normalised, so the file's rot_0..3 are the unit quaternion in
         DEVICE order.  gsplat_save_ply writes its (w,x,y,z) input as (x,y,z,w) (Gaussians' Eigen convention), so the
         columns are pre-rotated here to land unchanged."""
         from . import dataset
-        p = {k: v.detach().cpu().numpy() for k, v in self.params.items()}
+        params = dict(self.params)
+        if self.cfg["filter3d"] and not raw and self.num_gaussians:
+            params["scale"], params["opacity"] = ops.filter3d_apply(params["scale"], params["opacity"], self.filter3d)
+        p = {k: v.detach().cpu().numpy() for k, v in params.items()}
         q = p["quaternion"].astype(np.float32)
         norm = np.sqrt((q.astype(np.float64) ** 2).sum(1, keepdims=True))
         q = (q / np.where(norm > 0, norm, 1.0)).astype(np.float32)

@@ -707,6 +707,54 @@ int gsplat_compute_conic_antialiased_backward(const float *J, const float *sigma
                                               const float *conic_grad_out, const float *compensation_grad_out, int N,
                                               float *J_grad_in, float *sigma_grad_in, void *stream);
 
+/* 3D smoothing filter (no ABI bump: new entry points only): the other half of Mip-Splatting.  Every gaussian is
+ * band-limited to the sampling rate of the training cameras that see it.  For gaussian i and camera k (view [R|t], proj,
+ * focal_x, width W, height H), with (x, y, z) the camera-space position and (u, v) the pixel coordinates the forward
+ * computes, camera k SAMPLES i when z > near, -0.15 W <= u <= 1.15 W and -0.15 H <= v <= 1.15 H;
+ *   t_i = min over the sampling cameras of z / focal_x_k   (no camera samples i: the maximum of t over the sampled
+ *         gaussians, 0 when there is none),        filter3d[i] = sqrtf(0.2f) t_i.
+ * The filter is constant with respect to the camera a view is rendered from: with s_k = exp(scale_k), f = filter3d[i] and
+ * sigma = sigmoid(opacity) a gaussian enters the rasterizer with
+ *   scale_eff_k = 1/2 log(s_k^2 + f^2)              (Sigma_eff = Sigma + f^2 I, R being orthonormal),
+ *   rho3        = sqrt(prod s_k^2 / prod (s_k^2 + f^2)) = exp(sum_k (scale_k - scale_eff_k)),
+ *   opacity_eff = logit(o),  o = sigma rho3,
+ * and with w_k = s_k^2 / (s_k^2 + f^2), g_s / g_o the gradients with respect to the effective values and
+ * q = g_o / (1 - o) (0 where 1 - o == 0 in float):
+ *   grad_scale_k = g_s_k w_k + q (1 - w_k),        grad_opacity = q (1 - sigma).
+ * A row with f == 0 passes through both ways with its bits unchanged.
+ *   gsplat_compute_filter3d         views / projs [V,16] row-major, focal_x [V], sizes [V,2] = (width, height) ints, all
+ *                                   device arrays; near >= 0 (Mip-Splatting: 0.2) -> filter3d [N].  One thread per
+ *                                   gaussian walks all V cameras; no host read-back; the same bits in every run;
+ *   gsplat_filter3d_apply           (scale [N,3], opacity [N], filter3d [N]) -> scale_eff [N,3], opacity_eff [N];
+ *   gsplat_filter3d_apply_backward  the chain rule, IN PLACE on stored gradients: gradient row j (j < M) belongs to
+ *                                   gaussian rows[j] (rows == NULL: j) and lies at grad_scale + j * scale_stride (three
+ *                                   floats) and grad_opacity + j * opacity_stride, strides in floats: [M,3] / [M] arrays
+ *                                   of gsplat_gradients (3, 1) and columns 4..6 / 3 of twelve-float rows (12, 12) alike;
+ *   gsplat_context_set_filter3d     filter3d [N] in global order, device memory, caller-owned and valid until it is
+ *                                   replaced; NULL (the default) switches the mode off.  Read by the next
+ *                                   gsplat_rasterize_image; a backward follows the forward it belongs to.  The forward
+ *                                   first writes scale_eff / opacity_eff into two arrays of the workspace (allocated by the
+ *                                   first forward in the mode) and then runs, unchanged, on them: conic, radii, culling and
+ *                                   tile lists are those of the filtered gaussians, and in anti-aliased mode the
+ *                                   compositing opacity is sigma rho3 rho with rho of the filtered covariance.  Every
+ *                                   per-gaussian backward that recomputes from parameters (gsplat_backward_pass, _depth,
+ *                                   _camera, gsplat_backward_gaussians, _range, _camera, _split) reads the same two arrays
+ *                                   and then applies the chain rule to the scale and opacity gradients it has written
+ *                                   (when both were requested; _range: its slots; _split: the visible rows of `common` in
+ *                                   its range), so `gaussians` and the gradients are those of the RAW parameters.  The
+ *                                   camera gradient is that of the filtered image.  gsplat_backward_gaussians_adam (all
+ *                                   modes): GSPLAT_ERR_INVALID_ARG before anything is launched -- it would step the
+ *                                   parameters it differentiates, and those are the effective ones.
+ * The stand-alone operators are untouched: a host that drives them calls the two apply operators around them. */
+int gsplat_compute_filter3d(const float *xyz, int N, const float *views, const float *projs, const float *focal_x,
+                            const int *sizes, int V, float near_thresh, float *filter3d, void *stream);
+int gsplat_filter3d_apply(const float *scale, const float *opacity, const float *filter3d, int N, float *scale_eff,
+                          float *opacity_eff, void *stream);
+int gsplat_filter3d_apply_backward(const float *scale, const float *opacity, const float *filter3d, const int *rows,
+                                   int M, float *grad_scale, int scale_stride, float *grad_opacity, int opacity_stride,
+                                   void *stream);
+int gsplat_context_set_filter3d(gsplat_context *ctx, const float *filter3d);
+
 #ifdef __cplusplus
 }
 #endif
