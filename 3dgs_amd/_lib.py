@@ -214,6 +214,7 @@ SIGNATURES = {
                                               ctypes.POINTER(Gradients), _P, _P, _P]),
     "gsplat_backward_pass_camera": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _P, _P, _P, _F, _I,
                                          ctypes.POINTER(Gradients), _P, _P, _P]),
+    "gsplat_context_accumulate_contributions": (_I, [_P, _I, _P, _P, _P, _P]),
     "gsplat_context_set_absgrad": (_I, [_P, _I]),
     "gsplat_context_absgrad_uv": (_I, [_P, _P, _P]),
     "gsplat_pack_absgrad_norm": (_I, [_P, _I, _P, _P]),

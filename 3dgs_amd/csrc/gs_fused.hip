@@ -59,6 +59,8 @@ int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorte
                       const TileSegments *segments,
                       const DepthMaps *depth, bool absgrad);
 int launch_tile_segments(const int *ranges, const int *tops, int num_tiles, const TileSegments &seg, hipStream_t st);
+int launch_contributions(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
+                         int width, int height, float *weight_sum, float *weight_max, int *pixels, hipStream_t st);
 int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
 bool tile_order_supported(int num_tiles);
 // gs_filter3d.hip: the 3D smoothing filter's parameter transform and its chain rule (gsplat_context_set_filter3d)
@@ -194,6 +196,9 @@ struct gsplat_context {
   size_t S = 0;
   long long last_longest = -1;  // longest tile list of the last counting-sort forward (-1: unknown)
   bool have_forward = false;
+  // the last forward completed and its records, lists, stop indices and compact_to_global are still this context's: what
+  // gsplat_context_accumulate_contributions replays (true after a render-only forward too, which leaves no have_forward)
+  bool lists_ready = false;
   // r05: the thirteen arrays of the reference's ForwardPassData (cuda_data.cuh:70-86).  They are pooled buffers, so that
   // gsplat_context_detach_forward_outputs can hand their blocks to the caller instead of the caller copying them.
   void forward_outputs(gs::DeviceBuffer *out[13]) {
@@ -2044,7 +2049,7 @@ static int check_forward_args(const gsplat_context *c, const gsplat_gaussians *g
 // The recorded forward is void from here on; outputs the caller took over (gsplat_context_detach_forward_outputs) come
 // back from the pool, at their old sizes
 static int reclaim_outputs(gsplat_context *c, hipStream_t st) {
-  c->have_forward = c->rows_ready = c->order_ready = c->depth_ready = c->rows_depth = c->rows_abs = false;
+  c->have_forward = c->lists_ready = c->rows_ready = c->order_ready = c->depth_ready = c->rows_depth = c->rows_abs = false;
   gs::pool_unwatch(&c->last_mask);
   c->last_mask = nullptr;  // rank[] and compact_to_global are about to be overwritten
   gs::DeviceBuffer *outs[13];
@@ -2415,6 +2420,7 @@ static void record_forward(gsplat_context *c, const FwdCall &f, const gs::Forwar
   gs::pool_watch(c->last_mask, &c->last_mask);  // cleared when whoever ends up owning the block returns it to the pool
   c->tan_fovx = f.tan_fovx; c->tan_fovy = f.tan_fovy; c->mh_dist = f.cfg->mh_dist;
   c->have_forward = !f.ro;  // a render-only forward leaves nothing for a backward
+  c->lists_ready = true;
   c->depth_ready = c->depth;
   if (!out) return;
   const bool mid = f.mid;
@@ -2506,6 +2512,7 @@ int gsplat_context_detach_forward_outputs(gsplat_context *c) {
   c->forward_outputs(outs);
   for (gs::DeviceBuffer *b : outs) (void)b->detach();  // the caller owns the blocks now (gsplat_pool_free)
   c->have_forward = false;  // the fused backward would read arrays this context no longer has
+  c->lists_ready = false;
   c->rows_ready = false;
   return GSPLAT_OK;
 }
@@ -2891,6 +2898,21 @@ int gsplat_pack_absgrad_norm(gsplat_context *c, int num_gaussians, float *uv_nor
       c->mask.as<unsigned char>(), c->rank.as<int>(), num_gaussians, c->grad_rows.as<float4>(), uv_norm);
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;
+}
+
+int gsplat_context_accumulate_contributions(gsplat_context *c, int num_gaussians, float *weight_sum, float *weight_max,
+                                            int *pixels, void *stream) {
+  // (every check before the launch: a refused call leaves the caller's arrays as they were)
+  GS_REQUIRE(c != nullptr, "null context");
+  GS_REQUIRE(weight_sum || weight_max || pixels, "no statistic asked for: weight_sum, weight_max and pixels are all NULL");
+  GS_REQUIRE(c->lists_ready, "no forward pass recorded in this context");
+  GS_REQUIRE(num_gaussians == c->N, "does not match the recorded forward");
+  if (weight_sum) GS_REQUIRE_DEV(weight_sum);
+  if (weight_max) GS_REQUIRE_DEV(weight_max);
+  if (pixels) GS_REQUIRE_DEV(pixels);
+  return gs::launch_contributions(c->recs.as<float4>(), c->sorted.as<int>(), c->ranges.as<int>(), c->n_px.as<int>(),
+                                  c->c2g.as<int>(), c->width, c->height, weight_sum, weight_max, pixels,
+                                  (hipStream_t)stream);
 }
 
 int gsplat_context_depth_map(gsplat_context *c, const float **depth) {

@@ -1835,6 +1835,109 @@ int launch_fwd_segments_table(const int *ranges, int num_tiles, const FwdSegment
   return GSPLAT_OK;
 }
 
+// ---- per-gaussian blend-weight statistics of a recorded forward (gsplat_context_accumulate_contributions) -------------
+// The forward's loop once more, reduced per gaussian instead of per pixel: one workgroup per tile, lanes on pixels and
+// batches of kBatch staged records as in render_fwd_kernel (same load_record / block_hits / stage_record / row lists, so
+// the same (gaussian, block) pairs are visited and alpha and T come out bit for bit -- T exactly for a list the forward
+// walked whole; a segmented forward multiplied its segments' products in another order).  A pixel takes part in entry i
+// of its tile's list iff i < n(p), the forward's stop index, and alpha passes the forward's 1/255 test; its weight is
+// alpha * T(before).  Per trip every 16-lane row holds one (gaussian, 4x4 block) pair: the row's sum (row_sum), maximum
+// (row_max_int on the bit pattern: weights are >= 0) and pixel count (the row's 16 bits of the ballot) go from the row's
+// first lane into the batch's three LDS accumulators (the four rows of a wave are on four different gaussians, so the
+// LDS atomic IS the step across the wave and across the four waves), and behind the batch thread t < count sends slot
+// t's totals to the caller's arrays at compact_to_global: one global atomic per statistic and (tile, gaussian), none
+// when no pixel of the tile composited the gaussian.  The sum is a float atomic (order-dependent in its last bits); the
+// maximum and the count are exact whatever the order.
+// The walk ends at the tile's largest stop index.  A list longer than kSegSplitMin is walked whole by this one workgroup
+// (correct, and as slow as the unsegmented forward was on such lists).
+__global__ __launch_bounds__(256) void contributions_kernel(const float4 *__restrict__ recs, const int *__restrict__ sorted,
+                                                            const int *__restrict__ ranges, const int *__restrict__ n_px,
+                                                            const int *__restrict__ c2g, int width, int height, int ntx,
+                                                            int num_tiles, float *__restrict__ weight_sum,
+                                                            unsigned int *__restrict__ weight_max, int *__restrict__ pixels) {
+  // r0 = (u, v, a2, b2) as staged; r1 = (c2, log2 opa, the exponent's bound, block-hit bits); [kBatch]: the sentinel
+  __shared__ float4 s_r0[kBatch + 1], s_r1[kBatch + 1];
+  __shared__ float s_sum[kBatch + 1];
+  __shared__ int s_max[kBatch + 1], s_cnt[kBatch + 1], s_gid[kBatch];
+  __shared__ int s_tile_top;
+  __shared__ __attribute__((aligned(16))) unsigned short s_list[16 * kListStride + 2];
+  const int tile = ordered_tile(nullptr, (int)blockIdx.x, num_tiles);
+  if (tile >= num_tiles) return;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, row = lane >> 4, j = lane & 15;
+  if (tid == 0) {
+    s_r0[kBatch] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    s_r1[kBatch] = sentinel_r1();
+    s_tile_top = 0;
+  }
+  const int tile_x = tile % ntx, tile_y = tile / ntx;
+  const int px = tile_x * 16 + (wave & 1) * 8 + (row & 1) * 4 + (j & 3);
+  const int py = tile_y * 16 + (wave >> 1) * 8 + (row >> 1) * 4 + (j >> 2);
+  const bool inside = px < width && py < height;
+  const float fpx = (float)px, fpy = (float)py;
+  const float tx0 = (float)(tile_x * 16), ty0 = (float)(tile_y * 16);
+  const char *r0b = reinterpret_cast<const char *>(s_r0), *r1b = reinterpret_cast<const char *>(s_r1);
+  const int start = ranges[tile], total = ranges[tile + 1] - start;
+  const int n = inside ? min(n_px[py * width + px], total) : 0;
+  // the rows' and the tile's largest stop index: a row builds no list beyond its own, the workgroup leaves at the tile's
+  const int row_top = row_max_int(n);
+  const int top0 = __builtin_amdgcn_readlane(row_top, 0), top1 = __builtin_amdgcn_readlane(row_top, 16);
+  const int top2 = __builtin_amdgcn_readlane(row_top, 32), top3 = __builtin_amdgcn_readlane(row_top, 48);
+  __syncthreads();
+  if (lane == 0) atomicMax(&s_tile_top, max(max(top0, top1), max(top2, top3)));
+  __syncthreads();
+  const int top = s_tile_top;
+  const RawSplats none = {nullptr, nullptr, nullptr, nullptr};
+  unsigned short *lists = s_list + wave * 4 * kListStride;
+  const unsigned short *my_list = lists + row * kListStride;
+  float T = inside ? 1.0f : 0.0f;
+  for (int base = 0; base < top; base += kBatch) {
+    const int count = min(kBatch, top - base);
+    __syncthreads();  // the flush of the batch before has read the accumulators
+    if (tid < count) {
+      const int g = sorted[start + base + tid];
+      SplatRec s = load_record<true>(g, recs, none);
+      const unsigned int hits = block_hits(s, tx0, ty0);  // (recomputed as the forward does: a render-only forward stores none)
+      stage_record(s);
+      s_r0[tid] = s.r0;
+      s_r1[tid] = make_float4(s.r1.x, s.r1.y, s.r1.y > kLog2AlphaMax ? kLog2AlphaMax : s.r1.y, __uint_as_float(hits));
+      s_gid[tid] = g;
+    }
+    if (tid <= kBatch) { s_sum[tid] = 0.0f; s_max[tid] = 0; s_cnt[tid] = 0; }
+    __syncthreads();
+    const RowCounts rc = build_row_lists<kListStride>(s_r1, lists, count, wave, lane, top0 - base, top1 - base, top2 - base,
+                                                      top3 - base, 1);
+    const int trips = max(max(rc.c0, rc.c1), max(rc.c2, rc.c3));
+    for (int i = 0; i < trips; ++i) {
+      const int off = my_list[i];  // a row past the end of its list reads the sentinel record: alpha 0
+      const float4 a = *reinterpret_cast<const float4 *>(r0b + off), b = *reinterpret_cast<const float4 *>(r1b + off);
+      float al = staged_alpha_capped(a.z, a.w, b.x, b.y, b.z, a.x - fpx, a.y - fpy);
+      const bool on = al > kAlphaMin && base + (off >> 4) < n;
+      al = on ? al : 0.0f;
+      const float w = al * T;
+      T = __builtin_fmaf(-al, T, T);
+      const float sum = row_sum(w);
+      const int top_w = row_max_int(__float_as_int(w));
+      const int cnt = __popc((unsigned int)(__ballot(on) >> (row * 16)) & 0xFFFFu);
+      if (j == 0 && cnt > 0) {
+        const int slot = off >> 4;
+        atomicAdd(&s_sum[slot], sum);
+        atomicMax(&s_max[slot], top_w);
+        atomicAdd(&s_cnt[slot], cnt);
+      }
+    }
+    __syncthreads();
+    if (tid < count) {
+      const int cnt = s_cnt[tid];
+      if (cnt > 0) {
+        const int gi = c2g[s_gid[tid]];
+        if (weight_sum) atomicAdd(weight_sum + gi, s_sum[tid]);
+        if (weight_max) atomicMax(weight_max + gi, (unsigned int)s_max[tid]);
+        if (pixels) atomicAdd(pixels + gi, cnt);
+      }
+    }
+  }
+}
+
 // host-side launchers shared with gs_fused.hip ------------------------------------------
 int launch_render_fwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, int width,
                       int height, float bg, int *n_out, float *T_out, float *image, hipStream_t st, float4 *zero,
@@ -1923,6 +2026,16 @@ int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorte
   } else {
     render_bwd_kernel<false, false, GS_BWD_BATCH><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
   }
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int launch_contributions(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
+                         int width, int height, float *weight_sum, float *weight_max, int *pixels, hipStream_t st) {
+  const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
+  contributions_kernel<<<dim3(tile_grid(num_tiles)), dim3(256), 0, st>>>(recs, sorted, ranges, n_px, c2g, width, height, ntx,
+                                                                         num_tiles, weight_sum,
+                                                                         reinterpret_cast<unsigned int *>(weight_max), pixels);
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;
 }

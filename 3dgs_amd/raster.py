@@ -209,6 +209,27 @@ class RasterContext:
         check(self._lib.gsplat_context_absgrad_uv(self._h, _ptr(out), st))
         return out
 
+    def accumulate_contributions(self, weight_sum=None, weight_max=None, pixels=None):
+        """Per-gaussian blend-weight statistics of the last forward, accumulated INTO the given [N] device tensors in
+        global gaussian order (gsplat_context_accumulate_contributions): weight_sum (float32) += sum over the pixels of
+        alpha * T, weight_max (float32) = max with the largest alpha * T, pixels (int32) += the number of pixels that
+        composited the gaussian.  Rows of culled gaussians are untouched, so the arrays can gather a camera set: clear
+        them once, call after each view's forward.  weight_max and pixels are bit-reproducible, weight_sum is a float
+        atomic sum.  Any of the three may be None, not all.  Works after any forward (render-only included) and after
+        its backward."""
+        for name, t, dt in (("weight_sum", weight_sum, torch.float32), ("weight_max", weight_max, torch.float32),
+                            ("pixels", pixels, torch.int32)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda
+                                  or not t.is_contiguous() or t.dim() != 1):
+                raise ValueError("%s must be a contiguous [N] %s device tensor or None" % (name, str(dt).split(".")[1]))
+        given = [t for t in (weight_sum, weight_max, pixels) if t is not None]
+        if any(t.numel() != given[0].numel() for t in given):
+            raise ValueError("weight_sum, weight_max and pixels must have the same length")
+        n = given[0].numel() if given else (self._last[0] if self._last else 0)
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self._lib.gsplat_context_accumulate_contributions(self._h, int(n), _ptr(weight_sum), _ptr(weight_max),
+                                                                _ptr(pixels), st))
+
     def set_preprocess_split(self, mode):
         """How the per-gaussian forward is launched: 0 (default) the single fused kernel, 1 SH colour then geometry on the
         caller's stream, 2 the two side by side on two streams (gsplat_context_set_preprocess_split); every output is

@@ -40,11 +40,26 @@ DEFAULT_CONFIG = dict(
     # smallest depth / focal length over the training views that see it (closer than filter3d_near: not seen), in
     # training and in evaluate().  f is recomputed every filter3d_interval iterations and whenever the gaussian set or
     # its order changes; the optimizer step runs behind the backward, as with antialiased
-    filter3d=False, filter3d_interval=100, filter3d_near=0.2)
+    filter3d=False, filter3d_interval=100, filter3d_near=0.2,
+    # prune_contribution: every prune_contribution_interval iterations from adaptive_control_end on (nothing regrows then
+    # and the last opacity reset is past), remove the gaussians that no pixel of any training view composites or whose
+    # largest blend weight alpha * T over all of them stays below prune_contribution_threshold
+    # (Trainer.prune_by_contribution; RasterContext.accumulate_contributions)
+    prune_contribution=False, prune_contribution_threshold=0.01, prune_contribution_interval=1000)
 
 
 def _logit(p):
     return math.log(p) - math.log(1.0 - p)
+
+
+def contribution_prune_mask(weight_max, pixels, threshold):
+    """The pruning policy on the two bit-reproducible statistics ([N] tensors, any device): True where a gaussian goes --
+    no pixel composited it, or its largest blend weight is below `threshold` (0: only the never-composited ones).  Never
+    everything: a mask that would leave no gaussian comes back all False."""
+    remove = (pixels == 0) | (weight_max < float(threshold))
+    if bool(remove.all()):
+        remove = torch.zeros_like(remove)
+    return remove
 
 
 def draw_view_indices(rng, iteration, world, num_views):
@@ -113,6 +128,7 @@ class Trainer:
         self.ctx_capacity = n
         self._new_optimizer(None)
         self.history = []
+        self.contribution_prunes = []  # (iteration, gaussians removed) of every scheduled prune_by_contribution
         self._set_filter3d(self.ctx)
 
     # ------------------------------------------------------------------ state
@@ -281,6 +297,8 @@ class Trainer:
         if it > c["reset_opacity_start"] and it % c["reset_opacity_interval"] == 0 and it < c["reset_opacity_end"]:
             self.reset_opacity()
             self.reset_grad_accum()
+        if c["prune_contribution"] and it >= c["adaptive_control_end"] and it % int(c["prune_contribution_interval"]) == 0:
+            self.contribution_prunes.append((it, self.prune_by_contribution()))
 
     def draw_views(self):
         return draw_view_indices(self.rng, self.iter, self.world, len(self.views))
@@ -318,6 +336,68 @@ class Trainer:
         finally:
             ctx.set_render_only(False)
         return total / len(views)
+
+    def contribution_scores(self, views=None):
+        """dict(weight_sum, weight_max, pixels): [N] device tensors, the blend-weight statistics of every gaussian
+        accumulated over `views` ((camera, image) pairs; default: all training views) -- sum and maximum of alpha * T
+        over the pixels that composite it, and their number (RasterContext.accumulate_contributions).  Rendered at
+        background 0 on the render-only context in the mode the run trains in (config keys antialiased, filter3d), as
+        evaluate() does; a view in which nothing is visible contributes nothing."""
+        n, dev = self.num_gaussians, self.params["xyz"].device
+        out = dict(weight_sum=torch.zeros(n, dtype=torch.float32, device=dev),
+                   weight_max=torch.zeros(n, dtype=torch.float32, device=dev),
+                   pixels=torch.zeros(n, dtype=torch.int32, device=dev))
+        if n == 0:
+            return out
+        ctx = self._context_for(n)
+        ctx.set_render_only(True)
+        try:
+            for cam, _ in (self.views if views is None else views):
+                try:
+                    ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
+                except Exception as e:  # no gaussian in view
+                    if getattr(e, "code", None) != -5:
+                        raise
+                    continue
+                ctx.accumulate_contributions(**out)
+        finally:
+            ctx.set_render_only(False)
+        return out
+
+    def prune_by_contribution(self, threshold=None, views=None, scores=None):
+        """Remove the gaussians that no pixel of `views` composites (pixels == 0) or whose largest blend weight over them
+        is below `threshold` (default: the config's prune_contribution_threshold; 0 removes only the never-composited
+        ones); `scores`: a contribution_scores() result to decide from instead of walking the views.  Survivors keep
+        their order; parameters, both Adam moments of every group and the densification statistics are compacted with
+        the same mask.  Never leaves zero gaussians: that prune changes nothing.  Returns the number removed.
+
+        The decision reads only weight_max and pixels, which carry the same bits in every run.  With world > 1 every
+        rank walks ALL training views itself and prunes from them, so the replicas stay bit-identical with no exchange."""
+        n = self.num_gaussians
+        if n == 0:
+            return 0
+        if scores is None:
+            scores = self.contribution_scores(views)
+        thr = self.cfg["prune_contribution_threshold"] if threshold is None else threshold
+        remove = contribution_prune_mask(scores["weight_max"], scores["pixels"], thr)
+        n_remove = int(remove.sum().item())
+        if n_remove == 0:
+            return 0
+        keep, keep_n = (~remove).to(torch.uint8).contiguous(), n - n_remove
+
+        def compact(t):
+            if t.numel() == 0:  # no SH coefficients yet
+                return t[:keep_n].contiguous()
+            stride = t.numel() // n
+            return ops.compact_masked_array(stride, t.reshape(-1), keep, keep_n).reshape((keep_n,) + tuple(t.shape[1:]))
+
+        self.params = {g: compact(t) for g, t in self.params.items()}
+        m = ({g: compact(self.opt.exp_avg[g]) for g in self.opt.names},
+             {g: compact(self.opt.exp_avg_sq[g]) for g in self.opt.names})
+        acc = (compact(self.opt.uv_grad_accum), compact(self.opt.grad_accum_dur.view(torch.float32)).view(torch.int32))
+        self._new_optimizer(m)
+        self.opt.uv_grad_accum, self.opt.grad_accum_dur = acc
+        return n_remove
 
     # ------------------------------------------------------------------ policy steps
     def reset_grad_accum(self):  # cuda/trainer.cu:233-236

@@ -518,6 +518,28 @@ int gsplat_backward_pass_camera(gsplat_context *ctx, const gsplat_gaussians *gau
                                 int l_max, const gsplat_gradients *out, float *grad_view, float *grad_campos,
                                 void *stream);
 
+/* Per-gaussian blend-weight statistics of the last completed forward (no ABI bump: a new entry point only): how much
+ * each gaussian contributed to the view, the number contribution-based pruning is built on.  Let visible gaussian j sit
+ * at position i of the list of the tile that holds pixel p.  j is composited at p iff i < splats_per_pixel[p] (the
+ * forward's own stop index) and its alpha at p passes the forward's 1/255 test; its blend weight there is
+ * w_jp = alpha_jp * T_p(before j), with alpha evaluated exactly as the forward evaluates it (0.99 cap included) on the
+ * opacity the forward's records carry (anti-aliased compensation and the 3D filter's factor included), and T running the
+ * forward's recurrence.  Per gaussian:
+ *   weight_sum[j]  sum_p w_jp            accumulated with +=   (float atomics: not bit-reproducible, as the gradient rows)
+ *   weight_max[j]  max_p w_jp            accumulated with max  (on the bit pattern, weights are >= 0 and never NaN:
+ *                                                               order-independent, bit-reproducible)
+ *   pixels[j]      pixels compositing j  accumulated with +=   (int32: bit-reproducible)
+ * weight_sum[j] is the pixel sum of the image that would render with colour 1 for j, 0 for every other gaussian and the
+ * background; hence sum_j weight_sum[j] = sum_p (1 - weight_per_pixel[p]).  The arrays are device arrays in GLOBAL
+ * gaussian order [num_gaussians], accumulated INTO (rows of culled gaussians are not touched): clear them once and call
+ * after each view's forward to gather statistics over a camera set.  Any of the three may be NULL, not all of them.
+ * num_gaussians must be the recorded forward's.  Works after a training, lean or render-only forward and after a backward
+ * of it; refused (GSPLAT_ERR_INVALID_ARG, before any launch) when there is no completed forward: none yet, the last one
+ * failed or saw nothing (GSPLAT_ERR_NO_VISIBLE), or its outputs were detached.  `stream` must be the forward's stream or
+ * ordered behind it.  A tile list longer than 1488 entries is walked whole by one workgroup. */
+int gsplat_context_accumulate_contributions(gsplat_context *ctx, int num_gaussians, float *weight_sum,
+                                            float *weight_max, int *pixels, void *stream);
+
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
  * tiles, stable radix sorts on (depth bits, tile).  1 / 2 force one route.  Both produce identical lists. */
