@@ -216,6 +216,7 @@ SIGNATURES = {
                                          ctypes.POINTER(Gradients), _P, _P, _P]),
     "gsplat_context_accumulate_contributions": (_I, [_P, _I, _P, _P, _P, _P]),
     "gsplat_context_set_absgrad": (_I, [_P, _I]),
+    "gsplat_context_set_compact_lists": (_I, [_P, _I]),
     "gsplat_context_absgrad_uv": (_I, [_P, _P, _P]),
     "gsplat_pack_absgrad_norm": (_I, [_P, _I, _P, _P]),
     "gsplat_context_set_antialiased": (_I, [_P, _I]),

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <cmath>
 #include <new>
+#include <vector>
 #include <rocprim/rocprim.hpp>
 #include <cstdlib>
 
@@ -50,7 +51,7 @@ struct RawSplats;
 int launch_render_fwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, int width,
                       int height, float bg, int *n_out, float *T_out, float *image, hipStream_t st, float4 *zero, long long zero_vec,
                       unsigned short *masks_out, const int *order, int *tops_out, const TileSegments *segments,
-                      const FwdSegments *fwd_segments, const DepthMaps *depth);
+                      const FwdSegments *fwd_segments, const DepthMaps *depth, const CompactLists *compact);
 int launch_fwd_segments_table(const int *ranges, int num_tiles, const FwdSegments &fs, hipStream_t st);
 int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, const int *n_px,
                       const float *T_px, const float *grad_image, int width, int height, float bg, float *rows,
@@ -100,6 +101,14 @@ struct gsplat_context {
   // by render_fwd, and the order table made from it right behind the forward (off the backward's critical path)
   gs::DeviceBuffer tile_tops, tile_order;
   bool order_ready = false;  // tile_order belongs to the recorded forward
+  // Compact lists for the backward (gs_render.h: CompactLists; gsplat_context_set_compact_lists): per instance the useful
+  // entries of every tile list and their block masks, per pixel the stop index counted in useful entries, per tile the
+  // useful entries its workgroup ranked.  ids_c and masks_c are instance buffers (reserve_instances, instance_room).
+  gs::DeviceBuffer ids_c, masks_c, n_c_px, tile_useful;
+  bool compact_lists = true;     // the switch; read by the next forward
+  bool compact_written = false;  // the last render_fwd launch wrote the compact arrays
+  bool compact_ready = false;    // ... and the recorded forward's backwards walk them
+  long long n_compact_backwards = 0;
   // r05: long lists split into segments for the backward (gs_render.h: TileSegments); allocated by the first forward that
   // follows one with a list beyond kSegSplitMin
   gs::DeviceBuffer seg_first, seg_extra, seg_chk;
@@ -209,6 +218,7 @@ struct gsplat_context {
     const gs::DeviceBuffer *all[] = {&mask, &counters, &rank, &xyz_c_all, &uv_all, &c2g, &xyz_c, &uv, &sigma, &conic, &J,
                                      &rgb, &radius, &recs, &counts, &offsets, &grad_rows, &hitmask, &keys_a, &keys_b, &pay_a, &pay_b,
                                      &sorted, &temp, &ranges, &image, &T_px, &n_px, &blockmasks, &kept, &tile_tops, &tile_order,
+                                     &ids_c, &masks_c, &n_c_px, &tile_useful,
                                      &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad, &cam_rows,
                                      &depth_map, &seg_chk_d, &fseg_part_d, &f3d_scale, &f3d_opacity};
     size_t b = 0;
@@ -221,6 +231,7 @@ struct gsplat_context {
     gs::DeviceBuffer *all[] = {&mask, &counters, &rank, &xyz_c_all, &uv_all, &c2g, &xyz_c, &uv, &sigma, &conic, &J,
                                &rgb, &radius, &recs, &counts, &offsets, &grad_rows, &hitmask, &keys_a, &keys_b, &pay_a, &pay_b,
                                &sorted, &temp, &bin_table, &ranges, &image, &T_px, &n_px, &blockmasks, &kept, &tile_tops, &tile_order,
+                                     &ids_c, &masks_c, &n_c_px, &tile_useful,
                                &seg_first, &seg_extra, &seg_chk, &fseg_first, &fseg_blocks, &fseg_gran, &fseg_part, &fseg_stop, &dir_grad, &cam_rows,
                                &depth_map, &seg_chk_d, &fseg_part_d, &f3d_scale, &f3d_opacity};
     for (auto *p : all) p->release();
@@ -246,6 +257,13 @@ constexpr int kBlock = 256;
 // GSPLAT_NO_TILE_ORDER=1: the backward takes its tiles in the plain XCD-run order (A/B of r04's heaviest-first order)
 bool gs_no_tile_order() {
   static const bool v = [] { const char *e = getenv("GSPLAT_NO_TILE_ORDER"); return e && e[0] == '1'; }();
+  return v;
+}
+
+// GSPLAT_NO_COMPACT_LISTS=1: the backward walks the full tile lists whatever the context's switch says (A/B of the compact
+// lists; gs_render.h: CompactLists)
+bool gs_no_compact_lists() {
+  static const bool v = [] { const char *e = getenv("GSPLAT_NO_COMPACT_LISTS"); return e && e[0] == '1'; }();
   return v;
 }
 
@@ -1811,6 +1829,8 @@ size_t instance_room(const gsplat_context *c) {
   room = std::min(room, c->pay_b.bytes / sizeof(unsigned long long));
   room = std::min(room, c->sorted.bytes / sizeof(int));
   room = std::min(room, c->blockmasks.bytes / sizeof(unsigned short));
+  room = std::min(room, c->ids_c.bytes / sizeof(int));
+  room = std::min(room, c->masks_c.bytes / sizeof(unsigned short));
   return room;
 }
 
@@ -1830,6 +1850,9 @@ int reserve_instances(gsplat_context *c, size_t S, int num_tiles, hipStream_t st
   if (c->pay_a.ptr != pay_before) GS_HIP(hipMemsetAsync(c->pay_a.ptr, 0, c->pay_a.bytes, st));
   if (c->sorted.ptr != sorted_before) GS_HIP(hipMemsetAsync(c->sorted.ptr, 0, c->sorted.bytes, st));
   if ((rc = c->blockmasks.reserve((S + 1) * sizeof(unsigned short)))) return rc;
+  // (the compact lists need no fill: the backward reads only the positions the forward it follows has written)
+  if ((rc = c->ids_c.reserve((S + 1) * sizeof(int)))) return rc;
+  if ((rc = c->masks_c.reserve((S + 1) * sizeof(unsigned short)))) return rc;
   if ((rc = c->temp.reserve(gs::binning_temp_bytes((size_t)c->max_gaussians, S ? S : 1, num_tiles)))) return rc;
   return GSPLAT_OK;
 }
@@ -1960,6 +1983,7 @@ int gsplat_context_create(gsplat_context **out, int max_gaussians, int max_width
   R(c->grad_rows, N * 64); R(c->hitmask, N * 8);
   R(c->ranges, (T + 1) * 4); R(c->image, P * 12); R(c->T_px, P * 4); R(c->n_px, P * 4);
   R(c->tile_tops, (T + 8) * 4); R(c->tile_order, (T + 8) * 4);
+  R(c->n_c_px, P * 4); R(c->tile_useful, (T + 8) * 4);
   if (!rc) {
     size_t sb1 = 0;
     (void)rocprim::exclusive_scan(nullptr, sb1, (int *)nullptr, (int *)nullptr, 0, N + 1, rocprim::plus<int>(), (hipStream_t)0);
@@ -2330,13 +2354,18 @@ static int queue_sparse_tail(gsplat_context *c, FwdCall &f, size_t cap, long lon
     dm.chk = split ? c->seg_chk_d.as<float>() : nullptr;
     dm.part = fsplit ? c->fseg_part_d.as<float>() : nullptr;
   }
+  // Compact lists for the backward (gs_render.h: CompactLists): the one-workgroup-per-tile forward of a training context
+  // writes them; a context that has seen a list beyond kSegSplitMin keeps the segment paths as they are.
+  const bool compact = !ro && c->compact_lists && !gs_no_compact_lists() && !split && !figures && !fsplit;
+  const gs::CompactLists cl = {c->ids_c.as<int>(), c->masks_c.as<unsigned short>(), c->n_c_px.as<int>(), c->tile_useful.as<int>()};
   r = gs::launch_render_fwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(), f.W, f.H, f.bg,
                             c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
                             c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)f.N * 4,  // M <= N is not known here yet
                             ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr,
                             (ordered || split || figures) ? c->tile_tops.as<int>() : nullptr, split ? &seg : nullptr,
-                            fsplit ? &fs : nullptr, c->depth ? &dm : nullptr);
+                            fsplit ? &fs : nullptr, c->depth ? &dm : nullptr, compact ? &cl : nullptr);
   if (r) return r;
+  c->compact_written = compact;
   c->seg_ready = split;
   c->seg_cap = seg.extra_cap;
   c->mark(4, true, st);
@@ -2404,8 +2433,9 @@ static int finish_radix_route(gsplat_context *c, const FwdCall &f, const gs::For
                              c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
                              c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)rec.M * 4,
                              f.ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr, nullptr, nullptr, nullptr,
-                             c->depth ? &f.dmap : nullptr);
+                             c->depth ? &f.dmap : nullptr, nullptr);
   if (rc) return rc;
+  c->compact_written = false;  // (the longest list is not known on this route: its backwards walk the full lists)
   c->seg_ready = false;
   c->mark(4, true, st);
   c->order_ready = false;
@@ -2488,6 +2518,9 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
     GS_HIP(hipMemsetAsync(c->keys_a.ptr, 0, sizeof(int), st));
     if ((rc = queue_sparse_tail(c, f, rec.S, rec.longest, false))) return rc;
   }
+  // The backward walks the compact lists of a forward whose own longest list stayed whole: a first forward with longer
+  // lists (the split follows the forward before) hands over the full lists, as it always has.
+  c->compact_ready = c->compact_written && rec.longest >= 0 && rec.longest <= gs::kSegSplitMin;
   record_forward(c, f, rec, out);
   return GSPLAT_OK;
 }
@@ -2567,15 +2600,19 @@ int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, con
   if (depth)
     dm = {c->xyz_c.as<float>(), c->depth_map.as<float>(), nullptr, c->seg_ready ? c->seg_chk_d.as<float>() : nullptr,
           grad_depth, grad_alpha};
-  int rc = gs::launch_render_bwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(),
-                                 c->n_px.as<int>(), c->T_px.as<float>(), grad_image, W, H, bg_color,
+  // compact lists (gs_render.h: CompactLists): the same kernel on the useful entries only -- ids, masks and stop indices
+  const bool compact = c->compact_ready && !c->seg_ready;
+  int rc = gs::launch_render_bwd(c->recs.as<float4>(), nullptr, compact ? c->ids_c.as<int>() : c->sorted.as<int>(),
+                                 c->ranges.as<int>(), compact ? c->n_c_px.as<int>() : c->n_px.as<int>(),
+                                 c->T_px.as<float>(), grad_image, W, H, bg_color,
                                  c->grad_rows.as<float>(), nullptr, nullptr, nullptr, nullptr, st,
-                                 c->blockmasks.as<unsigned short>(), timed ? c->ev[c->slot][12] : nullptr,
+                                 compact ? c->masks_c.as<unsigned short>() : c->blockmasks.as<unsigned short>(), timed ? c->ev[c->slot][12] : nullptr,
                                  timed ? c->ev[c->slot][13] : nullptr,
                                  (c->order_ready && !gs_no_tile_order()) ? c->tile_order.as<int>() : nullptr,
                                  c->seg_ready ? &seg : nullptr, depth ? &dm : nullptr, c->absgrad);
   if (rc) return rc;
   if (c->seg_ready) c->n_segmented_backwards++;
+  if (compact) c->n_compact_backwards++;
   if (c->order_ready && !gs_no_tile_order()) c->n_ordered_backwards++;
   if (timed) c->pending[c->slot][6] = 1;
   if (rgb_global) {
@@ -2867,6 +2904,12 @@ int gsplat_context_set_filter3d(gsplat_context *c, const float *filter3d) {
   return GSPLAT_OK;
 }
 
+int gsplat_context_set_compact_lists(gsplat_context *c, int enabled) {
+  GS_REQUIRE(c != nullptr, "null context");
+  c->compact_lists = enabled != 0;  // (read by the next forward; a backward follows the forward it belongs to)
+  return GSPLAT_OK;
+}
+
 int gsplat_context_set_absgrad(gsplat_context *c, int enabled) {
   GS_REQUIRE(c != nullptr, "null context");
   c->absgrad = enabled != 0;  // (read by the next compositing backward; the forward has no part in it)
@@ -2966,10 +3009,21 @@ int gsplat_context_get_counters(gsplat_context *c, long long *out, int n) {
   }
   int fallbacks = 0;  // (a blocking 4-byte copy: this is a diagnostic call)
   if (n > 9 && c->counters.ptr) GS_HIP(hipMemcpy(&fallbacks, c->fseg_fallbacks(), sizeof(int), hipMemcpyDeviceToHost));
-  const long long v[10] = {c->n_forwards, c->n_tail_redone, c->n_compact_walks, c->n_instance_growths, c->n_ordered_backwards,
-                           (long long)c->n_segmented_backwards, (long long)c->n_segmented_forwards, fmax, fsum, fallbacks};
-  for (int k = 0; k < n && k < 10; ++k) out[k] = v[k];
-  return 10;
+  // out[11]: the tiles' useful totals of the last forward that wrote compact lists, summed on request (a blocking copy of
+  // one int per tile behind everything queued on the device: a diagnostic call)
+  long long useful = 0;
+  if (n > 11 && c->compact_written && c->have_forward) {
+    const size_t tiles = (size_t)((c->width + 15) / 16) * ((c->height + 15) / 16);
+    std::vector<int> h(tiles);
+    GS_HIP(hipDeviceSynchronize());
+    GS_HIP(hipMemcpy(h.data(), c->tile_useful.ptr, tiles * sizeof(int), hipMemcpyDeviceToHost));
+    for (int u : h) useful += u;
+  }
+  const long long v[12] = {c->n_forwards, c->n_tail_redone, c->n_compact_walks, c->n_instance_growths, c->n_ordered_backwards,
+                           (long long)c->n_segmented_backwards, (long long)c->n_segmented_forwards, fmax, fsum, fallbacks,
+                           c->n_compact_backwards, useful};
+  for (int k = 0; k < n && k < 12; ++k) out[k] = v[k];
+  return 12;
 }
 
 int gsplat_context_set_render_only(gsplat_context *c, int enabled) {

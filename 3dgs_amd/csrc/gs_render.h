@@ -618,4 +618,19 @@ struct DepthMaps {
   const float *grad_alpha;  // [H,W] backward: dL/d alpha (null: zero)
 };
 
+// Compact lists for the backward (gsplat_context_set_compact_lists).  The tile lists come from the reference's box test,
+// and about a quarter of their entries (benchmark scene: 23.7 %) reach no 4x4 block of their tile with alpha >= 1/255:
+// block_hits gives them an empty mask, they enter no row list, and they add nothing to the image or to any gradient.  The
+// backward still staged them, gave them a slot of its batches and flushed their zeros.  The forward, which computes every
+// entry's mask anyway, therefore writes each tile's USEFUL entries (mask != 0), in list order, to the front of the tile's
+// own range of `ids` / `masks`, and per pixel the stop index counted in useful entries: render_bwd_kernel given these three
+// arrays in place of sorted / masks / n walks only the useful entries, with the same per-pixel arithmetic.  The full lists,
+// masks and stop indices are written as ever (parity outputs; contributions_kernel reads them).
+struct CompactLists {
+  int *ids;               // [instances]: per tile, the useful entries of its list, a prefix of [ranges[t], ranges[t + 1])
+  unsigned short *masks;  // [instances]: their block masks, same positions
+  int *n_px;              // [H,W]: useful entries in front of and including the one that saturated the pixel
+  int *count;             // [num_tiles]: useful entries the tile's workgroup ranked (all of them unless every pixel saturated)
+};
+
 }  // namespace gs

@@ -439,10 +439,21 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
   *stop = T_fin >= 0.0f ? n : (alive ? -1 : -2);
 }
 
+__device__ __forceinline__ int row_max_int(int v) {  // max over the 16 lanes of a row, in every lane of the row
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));
+  return v;
+}
+
 #ifndef GS_FWD_WAVES
 #define GS_FWD_WAVES 8
 #endif
-template <bool kPacked, bool kDepth = false>
+// kCompact: the forward also writes the compact lists for the backward (gs_render.h: CompactLists).  An instantiation of
+// its own, for the scalar registers: the kernel sits at the 8-waves budget of both register files, and the compact form
+// pays for its pointers and its running count with what the segment paths -- which it never runs beside -- hold.
+template <bool kPacked, bool kDepth = false, bool kCompact = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVES, 8))) void render_fwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
                                                               const int *__restrict__ sorted,
                                                               const int *__restrict__ ranges, int width, int height,
@@ -451,10 +462,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
                                                               float *__restrict__ image, float4 *__restrict__ zero,
                                                               long long zero_vec, unsigned short *__restrict__ masks_out,
                                                               const int *__restrict__ order, int *__restrict__ tops_out,
-                                                              TileSegments seg, FwdSegments fs, DepthMaps dm) {
+                                                              TileSegments seg, FwdSegments fs, DepthMaps dm,
+                                                              CompactLists cl) {
   static_assert(kPacked || !kDepth, "depth mode is a mode of the context's (packed) kernels");
+  static_assert(kPacked || !kCompact, "compact lists are written by the context's (packed) forward");
   __shared__ float4 s_r0[kBatch + 1], s_r1[kBatch + 1], s_r2[kBatch + 1];  // [kBatch]: the all-zero sentinel record
   __shared__ int s_tile_top;
+  __shared__ int s_useful[4];  // compact lists (gs_render.h: CompactLists): the batch's useful slots, per staging wave
   __shared__ __attribute__((aligned(16))) unsigned short s_list[16 * kListStride + 2];
   // Optional side job: every workgroup clears its share of `zero` (the gradient rows the backward accumulates into).
   // This kernel leaves most of the HBM bandwidth unused, so the 64 bytes per gaussian ride along for free instead of
@@ -466,8 +480,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
   // the segments of the long lists come first (gs_render.h: FwdSegments): each is a block of its own, and the tiles they
   // belong to have no block in the main grid
   // (the context's forward only: the stand-alone operator on the reference's arrays keeps one block per tile)
-  const bool segmented = kPacked && fs.blocks != nullptr;
-  if constexpr (kPacked) {
+  const bool segmented = kPacked && !kCompact && fs.blocks != nullptr;
+  if constexpr (kPacked && !kCompact) {
     if (segmented && (int)blockIdx.x < fs.cap) {
       if ((int)blockIdx.x < *fs.count)
         fwd_segment_block<kPacked, kDepth>(recs, raw, sorted, ranges, width, height, ntx, masks_out, fs, (int)blockIdx.x, s_r0, s_r1, s_r2, s_list, dm);
@@ -503,9 +517,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
   int n = total;
   unsigned long long satmask = __ballot(!inside);  // lanes whose pixel is saturated or outside the image
   int live = satmask != ~0ull ? 1 : 0;
+  // Compact lists (gs_render.h: CompactLists; the context's forward, one workgroup per tile): `cbase` counts the useful
+  // entries of the batches so far (workgroup-uniform).  A pixel's stop index counted in useful entries is stored by the
+  // batch that saturates it, behind the trip loop, and merged into the tile's maximum there: it is no register of the loop.
+  constexpr bool compact = kCompact;
+  int cbase = 0;
 
   static_assert(kSegEntries % kBatch == 0, "a segment boundary is a batch boundary of the forward");
-  const bool checkpoints = seg.chk != nullptr && total > kSegSplitMin;  // a long list: the backward may walk it in segments
+  const bool checkpoints = !kCompact && seg.chk != nullptr && total > kSegSplitMin;  // a long list: the backward may walk it in segments
   for (int base = 0; base < total; base += kBatch) {
     const int count = min(kBatch, total - base);
     // an opaque per-batch copy of the thread index (see render_bwd_kernel): staging and list-building addresses are
@@ -522,15 +541,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
 #endif
     __syncthreads();
     GS_LAP(st_bar);
+    int g = 0;
+    unsigned int hits = 0u;
     if (t < count) {
-      const int g = sorted[start + base + t];
+      g = sorted[start + base + t];
       SplatRec s = load_record<kPacked>(g, recs, raw);
 #if GS_STAMP
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // split the staging stamp: loads | block test + LDS stores
       asm volatile("" : "+v"(s.r0.x), "+v"(s.r1.x), "+v"(s.r2.x));
       GS_LAP(st_load);
 #endif
-      const unsigned int hits = block_hits(s, tx0, ty0);
+      hits = block_hits(s, tx0, ty0);
       if (masks_out) masks_out[start + base + t] = (unsigned short)hits;  // the backward stages the same instances
       stage_record(s);
       // The 0.99 cap goes into the exponent's own clamp (r04): alpha = exp2(min(q, log2 opa)) already has a per-gaussian
@@ -543,9 +564,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
       if constexpr (kDepth) s.r1.z = dm.xyz_c[3 * g + 2];  // (gs_render.h: DepthMaps; the loop never reads r1.z otherwise)
       s_r0[t] = s.r0; s_r1[t] = s.r1; s_r2[t] = s.r2;
     }
+    unsigned int rank = 0u;  // of a useful slot among its staging wave's useful slots, inclusive
+    if constexpr (kCompact) {
+      // The rank rides in the high half of r1.w, above the 16 block bits (build_row_lists tests single bits): it is in
+      // LDS before the barrier below, where the pixel that saturates on this slot -- a thread of any wave -- finds it.
+      // (a 4-byte store of its own behind the record's: nothing of the record stays in registers for it)
+      const unsigned long long useful = __ballot(hits != 0u);
+      rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(useful >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)useful, 0u)) + 1u;
+      if (hits != 0u) s_r1[t].w = __uint_as_float(hits | (rank << 16));
+      if ((t & 63) == 0) s_useful[t >> 6] = __popcll(useful);
+    }
     GS_LAP(st_stage);
     __syncthreads();
     GS_LAP(st_bar1);
+    if constexpr (kCompact) {
+      if (hits != 0u) {
+        const int w = t >> 6;
+        const size_t at = (size_t)start + cbase + (w > 0 ? s_useful[0] : 0) + (w > 1 ? s_useful[1] : 0) +
+                          (w > 2 ? s_useful[2] : 0) + (rank - 1u);
+        cl.ids[at] = g;
+        cl.masks[at] = (unsigned short)hits;
+      }
+    }
     if (live > 0) {
       // rows whose 16 pixels are all saturated (or outside) need no list
       const int big = kBatch;
@@ -622,14 +662,41 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
       }
     }
     GS_LAP(st_loop);
+    if constexpr (kCompact) {
+      // Once per batch, behind the trip loop (which stays what it is: on the benchmark scene most pixels saturate, and the
+      // trip that saturates one is not rare enough to carry this): a pixel that saturated in THIS batch -- on slot
+      // n - 1 - base, an entry of a row list, hence useful -- stores its stop index counted in useful entries, the entry's
+      // inclusive rank among the tile's useful ones.  The staged records and the staging waves' totals stand until the
+      // next batch is staged, behind the barrier at the top of the loop.
+      const int u0 = s_useful[0], u1 = s_useful[1], u2 = s_useful[2], u3 = s_useful[3];
+      int n_c = 0;
+      if (T_fin >= 0.0f && n > base) {
+        const int sl = n - 1 - base, w = sl >> 6;
+        n_c = cbase + (w > 0 ? u0 : 0) + (w > 1 ? u1 : 0) + (w > 2 ? u2 : 0) + (int)(__float_as_uint(s_r1[sl].w) >> 16);
+        // (the pixel's position from the batch's opaque copy of the thread index: px and py stay out of the loop's registers)
+        const int qx = tile_x * 16 + ((t >> 6) & 1) * 8 + ((t >> 4) & 1) * 4 + (t & 3);
+        const int qy = tile_y * 16 + (t >> 7) * 8 + ((t >> 5) & 1) * 4 + ((t >> 2) & 3);
+        cl.n_px[qy * width + qx] = n_c;
+      }
+      if (tops_out) {  // the tile's largest compact stop index (see below)
+        const int m = row_max_int(n_c);
+        const int wave_max = max(max(__builtin_amdgcn_readlane(m, 0), __builtin_amdgcn_readlane(m, 16)),
+                                 max(__builtin_amdgcn_readlane(m, 32), __builtin_amdgcn_readlane(m, 48)));
+        if ((t & 63) == 0 && wave_max > 0) atomicMax(&s_tile_top, wave_max);
+      }
+      cbase = __builtin_amdgcn_readfirstlane(cbase + u0 + u1 + u2 + u3);
+    }
     const int all_done = __syncthreads_and(live <= 0 ? 1 : 0);
     GS_LAP(st_bar2);
     if (all_done) break;
   }
+  // compact lists: a pixel that never saturated walks all of the tile's useful entries (its workgroup ranked every batch)
+  const bool compact_all = compact && inside && !(T_fin >= 0.0f);
   if (tops_out) {
     // the tile's work in the backward = the largest stop index of its pixels (cuda/render_backward.cu:64,74): handed to
-    // tile_order_kernel, which deals the backward's tiles heaviest first
-    int top = inside ? n : 0;
+    // tile_order_kernel, which deals the backward's tiles heaviest first (counted in useful entries when the backward
+    // walks the compact lists)
+    int top = compact ? (compact_all ? cbase : 0) : inside ? n : 0;  // (compact: the saturated pixels have merged theirs)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) top = max(top, __shfl_xor(top, off, 64));
     if (lane == 0) atomicMax(&s_tile_top, top);
@@ -645,7 +712,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
     image[3 * pid + 1] = ag + Tout * bg;
     image[3 * pid + 2] = ab + Tout * bg;
     if constexpr (kDepth) dm.depth[pid] = ad;  // (background 0)
+    if (compact_all) cl.n_px[pid] = cbase;
   }
+  if (compact && tid == 0) cl.count[tile] = cbase;
 #if GS_STAMP
   if (lane == 0) {
     unsigned long long *o = gs_stamp_fwd + ((size_t)blockIdx.x * 4 + wave) * GS_STAMP_WORDS;
@@ -654,14 +723,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
     o[11] = 0; o[12] = st_bar1; o[13] = st_bar2; o[14] = 0; o[15] = (unsigned long long)wave;
   }
 #endif
-}
-
-__device__ __forceinline__ int row_max_int(int v) {  // max over the 16 lanes of a row, in every lane of the row
-  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));
-  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));
-  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));
-  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));
-  return v;
 }
 
 // waves per SIMD the depth-mode backward is compiled for (gs_render.h: DepthMaps): at 8 it spills 38 registers in the
@@ -1942,20 +2003,26 @@ __global__ __launch_bounds__(256) void contributions_kernel(const float4 *__rest
 int launch_render_fwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, int width,
                       int height, float bg, int *n_out, float *T_out, float *image, hipStream_t st, float4 *zero,
                       long long zero_vec, unsigned short *masks_out, const int *order, int *tops_out, const TileSegments *segments,
-                      const FwdSegments *fwd_segments, const DepthMaps *depth) {
+                      const FwdSegments *fwd_segments, const DepthMaps *depth, const CompactLists *compact) {
   const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
+  const CompactLists cl = compact ? *compact : CompactLists{nullptr, nullptr, nullptr, nullptr};
+  GS_REQUIRE(!compact || (recs && !fwd_segments && !segments), "compact lists: the context's unsegmented forward only");
   RawSplats none = {nullptr, nullptr, nullptr, nullptr};
   const TileSegments seg = segments ? *segments : TileSegments{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
   const FwdSegments fs = fwd_segments ? *fwd_segments : FwdSegments{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0};
   const dim3 grid(tile_grid(num_tiles) + (fs.blocks ? fs.cap : 0)), block(256);
   const DepthMaps dm = depth ? *depth : DepthMaps{};
   GS_REQUIRE(recs || !depth, "depth mode needs the packed records");
-  if (recs && depth) {
-    render_fwd_kernel<true, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm);
+  if (recs && depth && compact) {
+    render_fwd_kernel<true, true, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm, cl);
+  } else if (recs && compact) {
+    render_fwd_kernel<true, false, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm, cl);
+  } else if (recs && depth) {
+    render_fwd_kernel<true, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm, cl);
   } else if (recs) {
-    render_fwd_kernel<true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm);
+    render_fwd_kernel<true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm, cl);
   } else {
-    render_fwd_kernel<false><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, nullptr, order, tops_out, seg, fs, dm);
+    render_fwd_kernel<false><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, nullptr, order, tops_out, seg, fs, dm, cl);
   }
   GS_LAUNCH_CHECK();
   if (fs.blocks) {
@@ -2067,7 +2134,7 @@ int gsplat_render_image(const float *uv, const float *opacity, const float *coni
   gs::RawSplats raw = {uv, opacity, conic, rgb};
   return gs::launch_render_fwd(nullptr, &raw, sorted_splats, splat_range_by_tile, image_width, image_height,
                                background_opacity, splats_per_pixel, weight_per_pixel, image, (hipStream_t)stream, nullptr,
-                               0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+                               0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -236,13 +236,21 @@ class RasterContext:
         bit-identical in all modes, 1 and 2 measure slower (profiles/r06_ab_preprocess_split.txt)."""
         check(self._lib.gsplat_context_set_preprocess_split(self._h, int(mode)))
 
+    def set_compact_lists(self, enabled):
+        """Compact lists for the compositing backward (gsplat_context_set_compact_lists; on by default): from the next
+        forward on, the backward walks only the tile-list entries that can touch a pixel of their tile.  Forward outputs
+        are the same bits either way, gradients the same sums in another order."""
+        check(self._lib.gsplat_context_set_compact_lists(self._h, int(bool(enabled))))
+
     def counters(self):
-        """What the context's forwards did so far (gsplat_context_get_counters)."""
-        v = (ctypes.c_longlong * 10)()
-        self._lib.gsplat_context_get_counters(self._h, v, 10)
+        """What the context's forwards did so far (gsplat_context_get_counters).  useful_entries is summed on the device's
+        results when asked for: this call waits for the device."""
+        v = (ctypes.c_longlong * 12)()
+        self._lib.gsplat_context_get_counters(self._h, v, 12)
         return dict(forwards=int(v[0]), tail_redone=int(v[1]), compact_walks=int(v[2]), instance_growths=int(v[3]),
                     ordered_backwards=int(v[4]), segmented_backwards=int(v[5]), segmented_forwards=int(v[6]),
-                    longest_chain=int(v[7]), chain_sum=int(v[8]), segment_fallbacks=int(v[9]))
+                    longest_chain=int(v[7]), chain_sum=int(v[8]), segment_fallbacks=int(v[9]),
+                    compact_list_backwards=int(v[10]), useful_entries=int(v[11]))
 
     def set_timing(self, enabled, stages=None):
         """Per-stage HIP-event timing on / off; `stages`: names from STAGES to time only those (each timed stage costs

@@ -626,8 +626,23 @@ int gsplat_context_set_preprocess_split(gsplat_context *ctx, int mode);
  * newest ones the host knows to be complete without synchronising, so the decision -- and with it the bits of the image
  * -- never follows host / GPU timing (r06).  out[9] segment workgroups of split forwards whose polls for the workgroup
  * in front ran out and which multiplied the transmittance product up themselves (results identical; every one of them
- * is work done twice).  Writes min(n, 10) values and returns 10. */
+ * is work done twice).  out[10] compositing backwards that walked compact lists (gsplat_context_set_compact_lists), out[11]
+ * the useful entries of the last forward's tile lists -- the sum over the tiles of what their workgroups ranked; 0 when
+ * that forward wrote no compact lists; asked for (n > 11), it waits for the device and copies one int per tile.  Writes
+ * min(n, 12) values and returns 12. */
 int gsplat_context_get_counters(gsplat_context *ctx, long long *out, int n);
+/* Compact lists for the compositing backward (new entry point, no signature changed; default on).  A tile list holds
+ * every gaussian whose mh_dist box touches the tile; about a quarter of the entries reach no 4x4 pixel block of the tile
+ * with alpha >= 1/255 and contribute nothing to the image or to any gradient.  With the switch on, the compositing forward
+ * of a training context also writes, per tile, the entries that can contribute, in list order, and per pixel the stop
+ * index counted in those; gsplat_backward_render* then walks only them.  Image, transmittance, stop indices and the lists
+ * of gsplat_forward_view are the same bits either way; gradients are the same sums with fewer zero terms (the order of the
+ * float atomics differs, as it does between any two runs).  Read by the next gsplat_rasterize_image; a backward follows
+ * its forward.  The full lists are used instead, silently, where compact ones are not written: render-only contexts, the
+ * radix binning route, and contexts whose last forward had a list beyond 1488 entries (the segment paths; a forward whose
+ * own longest list exceeds that hands over its full lists too).  GSPLAT_NO_COMPACT_LISTS=1 in the environment forces the
+ * switch off. */
+int gsplat_context_set_compact_lists(gsplat_context *ctx, int enabled);
 int gsplat_context_set_timing(gsplat_context *ctx, int enabled);
 /* The same for a subset of the stages (bit k of stage_mask = stage k; 0 switches timing off).  Every timed stage
  * costs two event records per call, about 0.7 % of a 1 ms step each: bench.py times only stage 6 inside its timed
