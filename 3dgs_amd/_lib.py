@@ -192,6 +192,10 @@ SIGNATURES = {
     "gsplat_density_masks": (_I, [_I, _P, _P, _P, _P, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P]),
     "gsplat_expand_sh": (_I, [_I, _I, _P, _P, _P]),
     "gsplat_gather_rows": (_I, [_I, _I, _P, _P, _P, _P]),
+    "gsplat_sample_by_weight": (_I, [_P, _I, _I, ctypes.c_ulonglong, _P, _P, _P]),
+    "gsplat_mcmc_relocate": (_I, [_I, _P, _P, _P, _F, _P]),
+    "gsplat_mcmc_add_noise": (_I, [_I, _P, _P, _P, _P, _F, ctypes.c_ulonglong, _P]),
+    "gsplat_mcmc_regularize": (_I, [_I, _P, _P, _P, _F, _F, _P, _P, _P]),
     "gsplat_compact_masked_array": (_I, [_P, _P, _I, _I, _P, ctypes.POINTER(_I), _P]),
     "gsplat_scatter_masked_array": (_I, [_P, _P, _I, _I, _P, _P]),
     "gsplat_context_create": (_I, [ctypes.POINTER(_P), _I, _I, _I]),

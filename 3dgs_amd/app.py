@@ -143,7 +143,7 @@ def main(argv=None, log=print):
     log(f"Attempting to read {config_path}")
     try:
         config = dataset.parseConfig(config_path)
-        config.update(dataset.parseExtensions(config_path))  # this project's optional keys (absgrad, antialiased, filter3d)
+        config.update(dataset.parseExtensions(config_path))  # this project's optional keys (dataset.EXTENSION_KEYS: absgrad, antialiased, filter3d, prune_contribution, mcmc)
     except dataset.HostError as e:
         print(f"Failed to load config file: {e}", file=sys.stderr)
         return 1

@@ -176,6 +176,123 @@ __global__ __launch_bounds__(kBlock) void gather_rows_kernel(long long total, in
   out[e] = in[(long long)order[r] * stride + (e - r * stride)];
 }
 
+// ---- MCMC densification ("3D Gaussian Splatting as Markov Chain Monte Carlo", Kheradmand et al. 2024; gsplat's
+// MCMCStrategy): sampling by weight, the opacity / scale correction of a relocation, the per-iteration position noise
+// and the opacity / scale regulariser.  The schedule (which rows are dead, how many to add) lives in
+// 3dgs_amd/trainer.py.  Everything random comes from the generator above, so a seed reproduces a step bit for bit.
+
+// uniform number `counter` of stream `seed` in [0, 1): the 53 high bits of normal_sample's word
+__device__ __forceinline__ double uniform_sample(unsigned long long seed, unsigned long long counter) {
+  const unsigned long long bits = splitmix64(splitmix64(seed) ^ (counter * 0xD1342543DE82EF95ull + 1ull));
+  return (double)(bits >> 11) * (1.0 / 9007199254740992.0);
+}
+
+// samples[k] = the smallest row whose inclusive prefix sum exceeds u_k * total: a row of weight zero repeats its
+// predecessor's sum and is never the smallest.  Every index written is in [0, N): the search never leaves it, whatever
+// the array holds.
+__global__ __launch_bounds__(kBlock) void sample_by_weight_kernel(const double *__restrict__ cdf, int N, int K,
+                                                                  unsigned long long seed, int *__restrict__ samples,
+                                                                  int *__restrict__ counts) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= K) return;
+  const double total = cdf[N - 1];
+  if (!(total > 0.0)) return;  // nothing to draw from (or NaN): write nothing
+  const double t = fmin(uniform_sample(seed, (unsigned long long)k) * total, nextafter(total, 0.0));
+  int lo = 0, hi = N - 1;  // cdf[N-1] = total > t: the answer exists and is <= hi
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (cdf[mid] > t) hi = mid;
+    else lo = mid + 1;
+  }
+  samples[k] = lo;
+  atomicAdd(&counts[lo], 1);
+}
+
+constexpr int kRelocateMaxN = 51;  // gsplat's N_MAX: a source drawn more often is corrected as if drawn 50 times
+
+// A gaussian of opacity o that is replaced by n coincident copies keeps the image when each copy has
+// o' = 1 - (1 - o)^(1/n) and its scale is multiplied by o / den (Kheradmand et al., eq. 9),
+//   den = sum_{i=1..n} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1)
+//       = sum_{k=0..n-1} C(n, k+1) (-1)^k o'^(k+1) / sqrt(k+1)        (hockey stick: sum_i C(i-1, k) = C(n, k+1)).
+// All in double: at n = 51 and o near 1 the alternating sum loses four digits, which float32 (gsplat's kernel) shows
+// and double does not.  C(n, k+1) is built by exact integer steps (every product stays below 2^53 for n <= 51).
+__global__ __launch_bounds__(kBlock) void mcmc_relocate_kernel(int N, float *__restrict__ opacity,
+                                                               float *__restrict__ scale,
+                                                               const int *__restrict__ counts, float min_opacity) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  const int cnt = counts[i];
+  if (cnt <= 0) return;
+  const int n = cnt < kRelocateMaxN - 1 ? cnt + 1 : kRelocateMaxN;
+  const double o = 1.0 / (1.0 + exp(-(double)opacity[i]));
+  if (!(o > 0.0)) return;  // cannot have been sampled (or NaN): left as it is
+  const double on = -expm1(log1p(-o) / (double)n);
+  double den = 0.0, binom = 1.0, power = 1.0;
+  for (int k = 0; k < n; ++k) {
+    binom = binom * (double)(n - k) / (double)(k + 1);  // C(n, k+1)
+    power *= on;                                        // o'^(k+1)
+    const double term = binom * power / sqrt((double)(k + 1));
+    den += (k & 1) ? -term : term;
+  }
+  const double shift = log(o / den);
+  for (int a = 0; a < 3; ++a) scale[3 * (size_t)i + a] = (float)((double)scale[3 * (size_t)i + a] + shift);
+  const double oc = fmin(fmax(on, (double)min_opacity), 1.0 - 1.1920929e-7);
+  opacity[i] = (float)log(oc / (1.0 - oc));
+}
+
+// xyz += Sigma nu,  Sigma = R diag(exp(scale))^2 R^T,  nu_a = normal * g * scaler with the gate
+// g = 1 / (1 + exp(100 (o - 0.005))) (gsplat's op_sigmoid(1 - o, k = 100, x0 = 0.995)): only nearly transparent
+// gaussians move.  R is formed as split_kernel forms it (which keeps its own copy: its draws are pinned bit for bit).
+// A closed gate (expf overflows from o = 0.893 on: g = 0) or scaler == 0 leaves the row's bits alone and reads nothing
+// more of it.
+__global__ __launch_bounds__(kBlock) void mcmc_add_noise_kernel(int N, float *__restrict__ xyz,
+                                                                const float *__restrict__ opacity,
+                                                                const float *__restrict__ scale,
+                                                                const float *__restrict__ quat, float scaler,
+                                                                unsigned long long seed) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= N) return;
+  const float o = 1.0f / (1.0f + expf(-opacity[i]));
+  const float g = 1.0f / (1.0f + expf(100.0f * (o - 0.005f)));
+  const float amp = g * scaler;
+  if (amp == 0.0f) return;
+  const float q0 = quat[4 * (size_t)i], q1 = quat[4 * (size_t)i + 1], q2 = quat[4 * (size_t)i + 2],
+              q3 = quat[4 * (size_t)i + 3];
+  const float inv = rsqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+  const float w = q0 * inv, x = q1 * inv, y = q2 * inv, z = q3 * inv;
+  const float r00 = 1.0f - 2.0f * (y * y + z * z), r01 = 2.0f * (x * y - w * z), r02 = 2.0f * (x * z + w * y);
+  const float r10 = 2.0f * (x * y + w * z), r11 = 1.0f - 2.0f * (x * x + z * z), r12 = 2.0f * (y * z - w * x);
+  const float r20 = 2.0f * (x * z - w * y), r21 = 2.0f * (y * z + w * x), r22 = 1.0f - 2.0f * (x * x + y * y);
+  const float ex = expf(scale[3 * (size_t)i]), ey = expf(scale[3 * (size_t)i + 1]), ez = expf(scale[3 * (size_t)i + 2]);
+  const float vx = ex * ex, vy = ey * ey, vz = ez * ez;
+  const float s00 = r00 * vx * r00 + r01 * vy * r01 + r02 * vz * r02;
+  const float s01 = r00 * vx * r10 + r01 * vy * r11 + r02 * vz * r12;
+  const float s02 = r00 * vx * r20 + r01 * vy * r21 + r02 * vz * r22;
+  const float s11 = r10 * vx * r10 + r11 * vy * r11 + r12 * vz * r12;
+  const float s12 = r10 * vx * r20 + r11 * vy * r21 + r12 * vz * r22;
+  const float s22 = r20 * vx * r20 + r21 * vy * r21 + r22 * vz * r22;
+  const unsigned long long c = (unsigned long long)i * 3ull;
+  const float n0 = normal_sample(seed, c) * g * scaler, n1 = normal_sample(seed, c + 1) * g * scaler,
+              n2 = normal_sample(seed, c + 2) * g * scaler;
+  xyz[3 * (size_t)i] += s00 * n0 + s01 * n1 + s02 * n2;
+  xyz[3 * (size_t)i + 1] += s01 * n0 + s11 * n1 + s12 * n2;
+  xyz[3 * (size_t)i + 2] += s02 * n0 + s12 * n1 + s22 * n2;
+}
+
+// gradients of w_opacity * sum sigmoid(opacity) + w_scale * sum exp(scale), added to the rows one view saw
+__global__ __launch_bounds__(kBlock) void mcmc_regularize_kernel(int M, const int *__restrict__ compact_to_global,
+                                                                 const float *__restrict__ opacity,
+                                                                 const float *__restrict__ scale, float w_opacity,
+                                                                 float w_scale, float *__restrict__ grad_opacity,
+                                                                 float *__restrict__ grad_scale) {
+  const int j = blockIdx.x * kBlock + threadIdx.x;
+  if (j >= M) return;
+  const size_t i = (size_t)compact_to_global[j];
+  const float s = 1.0f / (1.0f + expf(-opacity[i]));
+  grad_opacity[j] += w_opacity * s * (1.0f - s);
+  for (int a = 0; a < 3; ++a) grad_scale[3 * (size_t)j + a] += w_scale * expf(scale[3 * i + a]);
+}
+
 int check_attr(int N, int num_sh_coef, const unsigned char *mask, const int *write_ids, const Attr &in,
                const AttrOut &out, const char *fn) {
   if (N < 0 || num_sh_coef < 0) { gs::set_error("%s: invalid argument: negative size", fn); return GSPLAT_ERR_INVALID_ARG; }
@@ -274,6 +391,50 @@ int gsplat_gather_rows(int N, int stride, const int *order, const float *in, flo
   GS_REQUIRE(in != out, "gather_rows is not in place");
   const long long total = (long long)N * stride;
   gather_rows_kernel<<<gs::div_up(total, kBlock), kBlock, 0, (hipStream_t)stream>>>(total, stride, order, in, out);
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int gsplat_sample_by_weight(const double *cdf, int N, int K, unsigned long long seed, int *samples, int *counts,
+                            void *stream) {
+  GS_REQUIRE(N >= 0 && K >= 0, "negative size");
+  if (N == 0 || K == 0) return GSPLAT_OK;
+  GS_REQUIRE_DEV(cdf); GS_REQUIRE_DEV(samples); GS_REQUIRE_DEV(counts);
+  sample_by_weight_kernel<<<gs::div_up(K, kBlock), kBlock, 0, (hipStream_t)stream>>>(cdf, N, K, seed, samples, counts);
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int gsplat_mcmc_relocate(int N, float *opacity, float *scale, const int *counts, float min_opacity, void *stream) {
+  GS_REQUIRE(N >= 0, "negative size");
+  GS_REQUIRE(min_opacity > 0.0f && min_opacity < 1.0f, "min_opacity must lie in (0, 1)");
+  if (N == 0) return GSPLAT_OK;
+  GS_REQUIRE_DEV(opacity); GS_REQUIRE_DEV(scale); GS_REQUIRE_DEV(counts);
+  mcmc_relocate_kernel<<<gs::div_up(N, kBlock), kBlock, 0, (hipStream_t)stream>>>(N, opacity, scale, counts, min_opacity);
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int gsplat_mcmc_add_noise(int N, float *xyz, const float *opacity, const float *scale, const float *quaternion,
+                          float scaler, unsigned long long seed, void *stream) {
+  GS_REQUIRE(N >= 0, "negative size");
+  if (N == 0) return GSPLAT_OK;
+  GS_REQUIRE_DEV(xyz); GS_REQUIRE_DEV(opacity); GS_REQUIRE_DEV(scale); GS_REQUIRE_DEV(quaternion);
+  mcmc_add_noise_kernel<<<gs::div_up(N, kBlock), kBlock, 0, (hipStream_t)stream>>>(N, xyz, opacity, scale, quaternion,
+                                                                                 scaler, seed);
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int gsplat_mcmc_regularize(int M, const int *compact_to_global, const float *opacity, const float *scale,
+                           float w_opacity, float w_scale, float *grad_opacity, float *grad_scale, void *stream) {
+  GS_REQUIRE(M >= 0, "negative size");
+  if (M == 0) return GSPLAT_OK;
+  GS_REQUIRE_DEV(compact_to_global); GS_REQUIRE_DEV(opacity); GS_REQUIRE_DEV(scale);
+  GS_REQUIRE_DEV(grad_opacity); GS_REQUIRE_DEV(grad_scale);
+  mcmc_regularize_kernel<<<gs::div_up(M, kBlock), kBlock, 0, (hipStream_t)stream>>>(M, compact_to_global, opacity, scale,
+                                                                                  w_opacity, w_scale, grad_opacity,
+                                                                                  grad_scale);
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;
 }

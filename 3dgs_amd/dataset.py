@@ -201,7 +201,7 @@ def parseConfig(path):
 
 
 # keys this project adds to the flat `key: value` file; optional (ConfigParameters and its parser stay the reference's)
-EXTENSION_KEYS = dict(absgrad=False, antialiased=False, filter3d=False, prune_contribution=False)
+EXTENSION_KEYS = dict(absgrad=False, antialiased=False, filter3d=False, prune_contribution=False, mcmc=False)
 
 
 def parseExtensions(path):

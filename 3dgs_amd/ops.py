@@ -236,6 +236,65 @@ def gather_rows(src, order):
     return out
 
 
+def sample_by_weight(weights, K, seed, counts=None):
+    """K draws from the rows of `weights` ([N] non-negative device tensor) with probability proportional to the weight
+    (gsplat_sample_by_weight; the prefix sum is torch.cumsum in float64).  Returns (samples [K] int32, counts [N] int32:
+    how often each row was drawn; `counts` given: accumulated into that tensor instead); a row of weight zero is never
+    drawn, and a seed reproduces the draw bit for bit.
+    All weights zero: ValueError (a blocking read of the sum; this runs once per refinement step)."""
+    N, K = int(weights.shape[0]), int(K)
+    samples = torch.empty(K, dtype=torch.int32, device=weights.device)
+    if counts is None:
+        counts = torch.zeros(N, dtype=torch.int32, device=weights.device)
+    elif counts.dtype != torch.int32 or counts.numel() != N:
+        raise ValueError("counts must be int32 [N]")
+    if N == 0 or K == 0:
+        if K:
+            raise ValueError("sample_by_weight: no rows to draw from")
+        return samples, counts
+    cdf = torch.cumsum(weights.reshape(-1).to(torch.float64), 0).contiguous()
+    if not float(cdf[-1]) > 0.0:
+        raise ValueError("sample_by_weight: the weights sum to zero")
+    check(_lib.load().gsplat_sample_by_weight(_p(cdf), N, K, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(samples), _p(counts),
+                                              _stream()))
+    return samples, counts
+
+
+def mcmc_relocate(opacity, scale, counts, min_opacity=0.005):
+    """In place (gsplat_mcmc_relocate): row i with counts[i] > 0 gets the opacity logit and log-scales of one of
+    min(counts[i] + 1, 51) coincident copies that together render what it rendered; the other rows are not written."""
+    N = int(opacity.shape[0])
+    if counts.dtype != torch.int32 or counts.numel() != N or scale.numel() != 3 * N:
+        raise ValueError("counts must be int32 [N] and scale [N,3]")
+    check(_lib.load().gsplat_mcmc_relocate(N, _p(_f32(opacity, "opacity")), _p(_f32(scale, "scale")), _p(counts),
+                                           float(min_opacity), _stream()))
+
+
+def mcmc_add_noise(xyz, opacity, scale, quaternion, scaler, seed):
+    """In place on xyz (gsplat_mcmc_add_noise): xyz[i] += Sigma_i nu with nu = normal * gate(opacity_i) * scaler; only
+    nearly transparent gaussians move, and scaler == 0 leaves xyz bit-unchanged."""
+    N = int(xyz.shape[0])
+    if opacity.numel() != N or scale.numel() != 3 * N or quaternion.numel() != 4 * N or xyz.numel() != 3 * N:
+        raise ValueError("xyz [N,3], opacity [N], scale [N,3] and quaternion [N,4] must have the same N")
+    check(_lib.load().gsplat_mcmc_add_noise(N, _p(_f32(xyz, "xyz")), _p(_f32(opacity, "opacity")),
+                                            _p(_f32(scale, "scale")), _p(_f32(quaternion, "quaternion")), float(scaler),
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, _stream()))
+
+
+def mcmc_regularize(compact_to_global, opacity, scale, w_opacity, w_scale, grad_opacity, grad_scale, M=None):
+    """grad_opacity[j] += w_opacity * s (1 - s), grad_scale[j] += w_scale * exp(scale[i]) for j < M with
+    i = compact_to_global[j], s = sigmoid(opacity[i]) (gsplat_mcmc_regularize).  M defaults to the rows of grad_opacity."""
+    M = int(grad_opacity.shape[0]) if M is None else int(M)
+    if compact_to_global.dtype != torch.int32 or compact_to_global.numel() < M:
+        raise ValueError("compact_to_global must be int32 with at least M entries")
+    if grad_opacity.numel() < M or grad_scale.numel() < 3 * M:
+        raise ValueError("the gradient arrays are shorter than M rows")
+    check(_lib.load().gsplat_mcmc_regularize(M, _p(compact_to_global), _p(_f32(opacity, "opacity")),
+                                             _p(_f32(scale, "scale")), float(w_opacity), float(w_scale),
+                                             _p(_f32(grad_opacity, "grad_opacity")), _p(_f32(grad_scale, "grad_scale")),
+                                             _stream()))
+
+
 def compact_masked_array(stride, d_source, d_mask, num_culled=None):
     """compact_masked_array<STRIDE>(d_source, d_mask, num_culled) -> new tensor [num_culled*stride].  With num_culled
     given the count is trusted, as the reference's template does (cuda_data.cuh:106-127): no read-back, the call stays

@@ -2,8 +2,9 @@
 
 Only the SCHEDULE lives here (what runs at which iteration, config thresholds); every data-parallel step is a HIP
 kernel behind the C ABI: rasterize / loss / backward / masked Adam (rows a-f2) and, for the density policy, the masks,
-clone / split, compaction, SH band re-layout, Morton codes and the row gather of gs_density.hip.  torch is used for
-device memory and for the key sort of the Morton re-order.  There is no CPU fallback.
+clone / split, compaction, SH band re-layout, Morton codes and the row gather of gs_density.hip (config key mcmc: its
+sampling, relocation, noise and regulariser kernels).  torch is used for device memory, for the key sort of the Morton
+re-order and for the row copies of an MCMC refinement step.  There is no CPU fallback.
 
 Parity note: the reference's density control is not reproducible (cuRAND seeded from time(NULL), std::random_device for
 the view order), so this loop is judged statistically (PSNR, gaussian counts), not bit for bit; with a fixed seed it is
@@ -45,7 +46,16 @@ DEFAULT_CONFIG = dict(
     # and the last opacity reset is past), remove the gaussians that no pixel of any training view composites or whose
     # largest blend weight alpha * T over all of them stays below prune_contribution_threshold
     # (Trainer.prune_by_contribution; RasterContext.accumulate_contributions)
-    prune_contribution=False, prune_contribution_threshold=0.01, prune_contribution_interval=1000)
+    prune_contribution=False, prune_contribution_threshold=0.01, prune_contribution_interval=1000,
+    # mcmc: the densification of "3D Gaussian Splatting as Markov Chain Monte Carlo" (gsplat's MCMCStrategy) in place of
+    # clone / split / prune and the opacity reset: at the adaptive_control cadence the gaussians at or below
+    # mcmc_min_opacity are moved onto live ones drawn by opacity and the set grows by mcmc_grow_factor up to exactly
+    # max_gaussians (Trainer.mcmc_relocate, mcmc_grow); every iteration adds opacity-gated noise of the gaussian's own
+    # shape to the positions (scaled by mcmc_noise_lr * the position learning rate) and the gradient of
+    # mcmc_opacity_reg * mean sigmoid(opacity) + mcmc_scale_reg * mean exp(scale) to the rows the view saw.  One rank
+    # only; the optimizer step runs behind the backward, as with antialiased
+    mcmc=False, mcmc_min_opacity=0.005, mcmc_noise_lr=5e5, mcmc_grow_factor=1.05, mcmc_opacity_reg=0.01,
+    mcmc_scale_reg=0.01)
 
 
 def _logit(p):
@@ -60,6 +70,11 @@ def contribution_prune_mask(weight_max, pixels, threshold):
     if bool(remove.all()):
         remove = torch.zeros_like(remove)
     return remove
+
+
+def mcmc_growth(n, grow_factor, max_gaussians):
+    """How many gaussians one MCMC refinement step adds to n: up to int(grow_factor * n) in all, never past the cap."""
+    return max(0, min(int(max_gaussians), int(grow_factor * n)) - n)
 
 
 def draw_view_indices(rng, iteration, world, num_views):
@@ -104,6 +119,11 @@ class Trainer:
         self.fused_adam = int(__import__("os").environ.get("GSPLAT_FUSED_ADAM", "1") or 0)
         if self.cfg["antialiased"] or self.cfg["filter3d"]:
             self.fused_adam = 0  # whatever the environment says: the Adam-inside backward refuses the modes
+        if self.cfg["mcmc"]:
+            if self.world > 1:
+                raise ValueError("mcmc trains on one rank: the sharded optimizer steps have no place for its regulariser")
+            self.fused_adam = 0  # the regulariser is added to stored gradients, between the backward and the step
+        self.mcmc_steps = []  # (iteration, gaussians relocated, gaussians added) of every MCMC refinement step
         self._filter3d = None       # [N] device tensor of the current gaussians; None: to be (re)computed
         self._filter3d_cams = None  # the training views' device camera arrays, built once
         self._sharded = None  # (key, ViewShardedStep) for the current gaussian count / SH degree
@@ -228,7 +248,7 @@ class Trainer:
         grad_image = self._grad_image_for(H, W, gt_image.device)
         # the loss value is a blocking read-back: only fetched when the caller logs it
         loss = ops.fused_loss(fwd["image"], gt_image, H, W, float(c["ssim_frac"]), grad_image, blocking=want_loss)
-        fused_adam = 0 if c["antialiased"] or c["filter3d"] else self.fused_adam
+        fused_adam = 0 if c["antialiased"] or c["filter3d"] or c["mcmc"] else self.fused_adam
         if fused_adam == 3:
             # r06: the SH group's step in a kernel that reads the coefficient rows once (update + the sums the position
             # gradient needs), then the per-gaussian backward with the five small groups' steps inside: no gradient arrays
@@ -245,7 +265,14 @@ class Trainer:
             ctx.backward_pass(p, cam, grad_image, bg, self.l_max, grads)
             if c["absgrad"]:  # the optimizer kernel takes the norm of what it is given as grad_uv: the absolute sums
                 grads = dict(grads, uv=ctx.absgrad_uv())
+            if c["mcmc"]:
+                n = self.num_gaussians
+                ops.mcmc_regularize(fwd["compact_to_global"], p["opacity"], p["scale"], float(c["mcmc_opacity_reg"]) / n,
+                                    float(c["mcmc_scale_reg"]) / (3 * n), grads["opacity"], grads["scale"])
             self.opt.step(it, fwd, grads, campos=cam["campos"])
+            if c["mcmc"]:
+                ops.mcmc_add_noise(p["xyz"], p["opacity"], p["scale"], p["quaternion"],
+                                   float(c["mcmc_noise_lr"]) * self.opt.learning_rates(it)["xyz"], self._mcmc_seed(it))
         self.iter += 1
         return loss
 
@@ -288,15 +315,24 @@ class Trainer:
 
     def maintenance(self):
         """Density control and opacity reset at the reference's cadence (cuda/trainer.cu:1394-1406); call after
-        train_step.  Uses the iteration index the step just ran with."""
+        train_step.  Uses the iteration index the step just ran with.  Config key mcmc: relocation and growth at the
+        density cadence instead of both (every step is recorded in mcmc_steps)."""
         c, it = self.cfg, self.iter - 1
-        if it > c["adaptive_control_start"] and it % c["adaptive_control_interval"] == 0 and it < c["adaptive_control_end"]:
-            self.adaptive_density_step()
-            self.sort_gaussians()
-            self.reset_grad_accum()
-        if it > c["reset_opacity_start"] and it % c["reset_opacity_interval"] == 0 and it < c["reset_opacity_end"]:
-            self.reset_opacity()
-            self.reset_grad_accum()
+        density = it > c["adaptive_control_start"] and it % c["adaptive_control_interval"] == 0 and it < c["adaptive_control_end"]
+        if c["mcmc"]:  # relocation and growth at the same cadence; no thresholds, no opacity reset
+            if density:
+                relocated = self.mcmc_relocate()
+                added = self.mcmc_grow()
+                self.sort_gaussians()
+                self.mcmc_steps.append((it, relocated, added))
+        else:
+            if density:
+                self.adaptive_density_step()
+                self.sort_gaussians()
+                self.reset_grad_accum()
+            if it > c["reset_opacity_start"] and it % c["reset_opacity_interval"] == 0 and it < c["reset_opacity_end"]:
+                self.reset_opacity()
+                self.reset_grad_accum()
         if c["prune_contribution"] and it >= c["adaptive_control_end"] and it % int(c["prune_contribution_interval"]) == 0:
             self.contribution_prunes.append((it, self.prune_by_contribution()))
 
@@ -495,6 +531,62 @@ class Trainer:
             m[g], v[g] = m[g].reshape(tgt).contiguous(), v[g].reshape(tgt).contiguous()
         self._new_optimizer((m, v))
         return dict(pruned=n_prune, cloned=n_clone, split=n_split, skipped=False)
+
+    # ------------------------------------------------------------------ MCMC densification (config key mcmc)
+    def _mcmc_seed(self, it):
+        return self.seed * 1000003 + it
+
+    def mcmc_relocate(self, seed=None):
+        """Move the dead gaussians (opacity at or below mcmc_min_opacity) onto live ones drawn with probability
+        proportional to their opacity.  A source drawn c times and its c copies take the opacity and scale that make the
+        c + 1 of them render what the source rendered (ops.mcmc_relocate), the copies every other attribute of the source;
+        both Adam moments of the sources and the moved rows restart at zero.  seed: default, the one of the iteration the
+        last train_step ran.  Returns the number of gaussians moved (0 when none or all are dead)."""
+        c, n = self.cfg, self.num_gaussians
+        opacity = self.params["opacity"]
+        dead = opacity <= _logit(float(c["mcmc_min_opacity"]))
+        dead_idx = dead.nonzero().reshape(-1)
+        k = int(dead_idx.numel())
+        if k == 0 or k == n:
+            return 0
+        weights = torch.sigmoid(opacity).masked_fill(dead, 0.0)
+        samples, counts = ops.sample_by_weight(weights, k, self._mcmc_seed(self.iter - 1) if seed is None else seed)
+        ops.mcmc_relocate(opacity, self.params["scale"], counts, float(c["mcmc_min_opacity"]))
+        src = samples.long()
+        for t in self.params.values():  # after the update: the copies carry the new opacity and scale
+            if t.numel():
+                t[dead_idx] = t[src]
+        rows = torch.cat([src, dead_idx])
+        for g in self.opt.names:
+            self.opt.exp_avg[g][rows] = 0
+            self.opt.exp_avg_sq[g][rows] = 0
+        self._filter3d = None  # positions changed
+        return k
+
+    def mcmc_grow(self, seed=None):
+        """Add mcmc_growth(N, mcmc_grow_factor, max_gaussians) gaussians as copies of sources drawn with probability
+        proportional to their opacity, corrected like a relocation; the moments of the sources and the new rows are zero.
+        seed: default, the one of the last iteration plus 2^32.  Returns the number added."""
+        c, n = self.cfg, self.num_gaussians
+        k = mcmc_growth(n, float(c["mcmc_grow_factor"]), c["max_gaussians"])
+        if k == 0 or n == 0:
+            return 0
+        samples, counts = ops.sample_by_weight(torch.sigmoid(self.params["opacity"]), k,
+                                               self._mcmc_seed(self.iter - 1) + 2 ** 32 if seed is None else seed)
+        ops.mcmc_relocate(self.params["opacity"], self.params["scale"], counts, float(c["mcmc_min_opacity"]))
+        src = samples.long()
+
+        def moments(t):
+            t = torch.cat([t, torch.zeros((k,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)], 0)
+            t[src] = 0
+            return t
+
+        m = ({g: moments(self.opt.exp_avg[g]) for g in self.opt.names},
+             {g: moments(self.opt.exp_avg_sq[g]) for g in self.opt.names})
+        self.params = {g: torch.cat([t, t[src]], 0).contiguous() for g, t in self.params.items()}
+        self._new_optimizer(m)
+        self._context_for(n + k)
+        return k
 
     def sort_gaussians(self):  # cuda/trainer.cu:853-922: Morton order of the positions
         n = self.num_gaussians

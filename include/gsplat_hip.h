@@ -309,6 +309,43 @@ int gsplat_expand_sh(int N, int l_max_old, const float *sh_in, float *sh_out, vo
 /* sort_gaussians' gather (cuda/trainer.cu:793-851): out[i, :] = in[order[i], :] for rows of `stride` floats. */
 int gsplat_gather_rows(int N, int stride, const int *order, const float *in, float *out, void *stream);
 
+/* ---- MCMC densification ("3D Gaussian Splatting as Markov Chain Monte Carlo", Kheradmand et al. 2024; gsplat's
+ * MCMCStrategy): the four data-parallel pieces; the schedule is the host's (3dgs_amd/trainer.py, config key mcmc).
+ * Random numbers come from split_gaussians' counter-based generator: with
+ *   bits(seed, c) = splitmix64(splitmix64(seed) ^ (c * 0xD1342543DE82EF95 + 1))
+ * the uniform u(seed, c) = (double)(bits >> 11) * 2^-53 lies in [0, 1) and the normals are split_gaussians'.  A seed
+ * reproduces every call bit for bit.  N == 0 (K == 0, M == 0) returns GSPLAT_OK without a launch.
+ *
+ *   gsplat_sample_by_weight  cdf[N]: the inclusive prefix sum of non-negative weights, in double, device memory.  For
+ *                            k < K: t = min(u(seed, k) * cdf[N-1], nextafter(cdf[N-1], 0)), samples[k] = the smallest i
+ *                            with cdf[i] > t (a row of weight zero is never returned), counts[samples[k]] += 1 (integer
+ *                            atomics; counts[N] is accumulated into: the caller clears it).  cdf[N-1] > 0 is checked on
+ *                            the device: when it does not hold, nothing is written.
+ *   gsplat_mcmc_relocate     in place on the opacity logits [N] and log-scales [N,3]: row i with counts[i] > 0 becomes
+ *                            one of n = min(counts[i] + 1, 51) coincident gaussians that together render what it
+ *                            rendered: o = sigmoid(logit), o' = 1 - (1 - o)^(1/n),
+ *                            den = sum_{i=1..n} sum_{k=0..i-1} C(i-1, k) (-1)^k o'^(k+1) / sqrt(k+1),
+ *                            log-scale += log(o / den), logit = logit(clamp(o', min_opacity, 1 - 2^-23)); evaluated in
+ *                            double (gsplat: float32) and rounded once.  Rows with counts[i] <= 0 are not written.
+ *                            0 < min_opacity < 1.
+ *   gsplat_mcmc_add_noise    xyz[i] += Sigma nu in float, Sigma = R diag(exp(scale))^2 R^T with R from the normalised
+ *                            quaternion as in split_gaussians, nu_a = normal(seed, 3 i + a) * g * scaler, the gate
+ *                            g = 1 / (1 + exp(100 (sigmoid(opacity) - 0.005))): opaque gaussians stay where they are.
+ *                            A row with g * scaler == 0 keeps its bits (scaler == 0: all of xyz).
+ *   gsplat_mcmc_regularize   the gradient of w_opacity * sum sigmoid(opacity) + w_scale * sum exp(scale), added to
+ *                            compacted gradient rows: for j < M, i = compact_to_global[j] (trusted, like the optimizer
+ *                            step's), grad_opacity[j] += w_opacity * s (1 - s), grad_scale[3 j + a] += w_scale *
+ *                            exp(scale[3 i + a]).  NOTE the difference from gsplat, which regularises and steps every
+ *                            gaussian in every iteration: the Adam of this library is masked by visibility, so the
+ *                            term reaches only the rows the iteration's view saw. */
+int gsplat_sample_by_weight(const double *cdf, int N, int K, unsigned long long seed, int *samples, int *counts,
+                            void *stream);
+int gsplat_mcmc_relocate(int N, float *opacity, float *scale, const int *counts, float min_opacity, void *stream);
+int gsplat_mcmc_add_noise(int N, float *xyz, const float *opacity, const float *scale, const float *quaternion,
+                          float scaler, unsigned long long seed, void *stream);
+int gsplat_mcmc_regularize(int M, const int *compact_to_global, const float *opacity, const float *scale,
+                           float w_opacity, float w_scale, float *grad_opacity, float *grad_scale, void *stream);
+
 /* ------------------------------------------------------------- compaction templates --- */
 
 /* replaces compact_masked_array<STRIDE>  (cuda_data.cuh:106-127): stable compaction of src[N,stride] by mask[N]
