@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "gs_common.h"
+#include "gs_launch.h"
 #include "gs_math.h"
 
 namespace {

@@ -11,6 +11,7 @@
 // and per-gaussian kernels see ordinary parameters (gsplat_context_set_filter3d, gs_fused.hip).
 // Everything is one thread per gaussian.
 #include "gs_common.h"
+#include "gs_launch.h"
 #include "gs_math.h"
 
 namespace {

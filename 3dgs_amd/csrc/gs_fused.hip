@@ -18,59 +18,10 @@
 #include <cstdlib>
 
 #include "gs_common.h"
+#include "gs_launch.h"
 #include "gs_math.h"
 #include "gs_render.h"
 #include "gs_rows.h"
-
-namespace gs {
-// from gs_binning.hip / gs_render.hip
-size_t binning_temp_bytes(size_t N, size_t S, int num_tiles);
-int scan_counts(int N, const int *counts, int *offsets, void *temp, size_t temp_bytes, hipStream_t st);
-bool binning_supports_counting_sort(int num_tiles);
-bool binning_prefers_radix(size_t S, int num_tiles);
-bool binning_next_route_is_radix(bool was_counting_sort, size_t S, int num_tiles, long long longest);
-size_t binning_table_bytes(int num_tiles);
-int binning_offsets(int ntx, int nty, int *table, int *long_tiles, hipStream_t st);
-int binning_scatter_and_sort(const float *uv, const float *xyz_c, const float *radius,
-                             const unsigned long long *hitmask, const int *rank, int N, int ntx, int nty,
-                             const int *table, int *ranges, size_t S, unsigned long long *payload,
-                             int *long_tiles, int *sorted_out, long long longest, const int *m_total,
-                             const unsigned long long *pair_counters, unsigned long long *pub,
-                             unsigned long long ticket, hipStream_t st, const SortFork *fork, bool compact_walk,
-                             bool keys_ok);
-int emit_sort_ranges(const float *uv, const float *xyz_c, const float *radius, int ntx, int nty, int N,
-                     const unsigned char *mask, const int *rank, const int *offsets, size_t S, unsigned int *tkeys_a,
-                     unsigned int *tkeys_b, unsigned long long *pay_a, unsigned long long *pay_b, int *sorted_out,
-                     int *ranges, void *temp, size_t temp_bytes, hipStream_t st, bool already_emitted,
-                     const unsigned long long *hitmask);
-int launch_tile_emit(const float *uv, const float *xyz_c, const float *radius, int ntx, int nty, int N,
-                     const unsigned char *mask, const int *rank, const int *offsets,
-                     const unsigned long long *hitmask, long long capacity, unsigned int *tkeys,
-                     unsigned long long *payload, hipStream_t st);
-struct RawSplats;
-int launch_render_fwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, int width,
-                      int height, float bg, int *n_out, float *T_out, float *image, hipStream_t st, float4 *zero, long long zero_vec,
-                      unsigned short *masks_out, const int *order, int *tops_out, const TileSegments *segments,
-                      const FwdSegments *fwd_segments, const DepthMaps *depth, const CompactLists *compact);
-int launch_fwd_segments_table(const int *ranges, int num_tiles, const FwdSegments &fs, hipStream_t st);
-int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, const int *n_px,
-                      const float *T_px, const float *grad_image, int width, int height, float bg, float *rows,
-                      float *g_rgb, float *g_opacity, float *g_uv, float *g_conic, hipStream_t st,
-                      const unsigned short *masks_in, hipEvent_t ev_start, hipEvent_t ev_stop, const int *order,
-                      const TileSegments *segments,
-                      const DepthMaps *depth, bool absgrad);
-int launch_tile_segments(const int *ranges, const int *tops, int num_tiles, const TileSegments &seg, hipStream_t st);
-int launch_contributions(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
-                         int width, int height, float *weight_sum, float *weight_max, int *pixels, hipStream_t st);
-int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
-bool tile_order_supported(int num_tiles);
-// gs_filter3d.hip: the 3D smoothing filter's parameter transform and its chain rule (gsplat_context_set_filter3d)
-int launch_filter3d_apply(const float *scale, const float *opacity, const float *filter3d, int N, float *scale_eff,
-                          float *opacity_eff, hipStream_t st);
-int launch_filter3d_apply_bwd(const float *scale, const float *opacity, const float *filter3d, const int *rows, int M,
-                              float *grad_scale, int scale_stride, float *grad_opacity, int opacity_stride,
-                              bool at_gaussian, int first, int end, int span, hipStream_t st);
-}  // namespace gs
 
 // GSPLAT_PRE_SPLIT=0|1|2: the per-gaussian forward as one kernel (the default), as sh_colour_kernel + preprocess_geom_kernel
 // one behind the other, or side by side on two streams (r06: built, bit-identical, measured slower -- see sh_colour_kernel);
@@ -2270,6 +2221,44 @@ static int queue_counts(gsplat_context *c, const FwdCall &f, size_t &room) {
                               c->pay_a.as<unsigned long long>(), st);
 }
 
+// The context's arrays as the compositing kernels' option structs (gs_render.h).  The backward's split lists with room
+// for `extra_cap` further segments: the forward that writes the checkpoints adds what it publishes (asked, stats, tag)
+static gs::TileSegments backward_segments(gsplat_context *c, int extra_cap) {
+  gs::TileSegments seg = {};
+  seg.granted = c->seg_first.as<int>();
+  seg.extra = c->seg_extra.as<int2>();
+  seg.extra_count = reinterpret_cast<int *>(seg.extra + extra_cap);  // [extra_cap]: the count
+  seg.chk = c->seg_chk.as<float4>();
+  seg.image = c->image.as<float>();
+  seg.extra_cap = extra_cap;
+  return seg;
+}
+// What both routes' render_fwd launches share: the records and lists in, the per-pixel arrays out, the gradient rows to
+// clear on the side (`zero_vec` float4), the block masks unless the forward only renders, and depth mode
+static gs::RenderFwdArgs packed_forward_args(gsplat_context *c, const FwdCall &f, long long zero_vec) {
+  gs::RenderFwdArgs a = {};
+  a.recs = c->recs.as<float4>();
+  a.sorted = c->sorted.as<int>();
+  a.ranges = c->ranges.as<int>();
+  a.width = f.W; a.height = f.H; a.bg = f.bg;
+  a.n_out = c->n_px.as<int>();
+  a.T_out = c->T_px.as<float>();
+  a.image = c->image.as<float>();
+  if (c->rows_zeroed) a.zero = c->grad_rows.as<float4>();
+  a.zero_vec = zero_vec;
+  if (!f.ro) a.masks_out = c->blockmasks.as<unsigned short>();
+  a.depth = f.dmap;  // ({} unless the context renders depth)
+  return a;
+}
+static gs::CompactLists compact_lists(gsplat_context *c) {
+  gs::CompactLists cl = {};
+  cl.ids = c->ids_c.as<int>();
+  cl.masks = c->masks_c.as<unsigned short>();
+  cl.n_px = c->n_c_px.as<int>();
+  cl.count = c->tile_useful.as<int>();
+  return cl;
+}
+
 // Sparse route: placement, per-tile sorts and render_fwd, queued before the host knows S (gs::tail_needs_redo has the
 // protocol) and bounded by `cap`: `ranges` on the device are clamped to it (bin_scatter_kernel), so whatever S turns out
 // to be, the kernels stay inside the buffers.  Which long-list kernels to queue follows `longest_hint`; a forward whose
@@ -2307,7 +2296,8 @@ static int queue_sparse_tail(gsplat_context *c, FwdCall &f, size_t cap, long lon
   gs::take_figures(w, f.ticket, c->fig);
   unsigned long long *d_slot = c->d_pub + 8 + 4 * (f.ticket & 1ull);  // where THIS forward's kernels publish
   const unsigned int my_tag = (unsigned int)(f.ticket & 0xFFFFFFFFull);
-  gs::TileSegments seg = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, my_tag};
+  gs::TileSegments seg = {};
+  seg.tag = my_tag;
   const bool split = !ro && !gs_no_segments() && c->last_longest > gs::kSegSplitMin && num_tiles <= 16384;  // (the table kernels' reach)
   if (split) {
     const size_t slots = cap / gs::kSegEntries + 2;  // (gs_render.h: segment_slot)
@@ -2316,15 +2306,16 @@ static int queue_sparse_tail(gsplat_context *c, FwdCall &f, size_t cap, long lon
     if ((r = c->seg_extra.reserve((want + 2) * sizeof(int2)))) return r;  // [want]: the count
     if ((r = c->seg_chk.reserve(slots * 256 * sizeof(float4)))) return r;
     if (c->depth && (r = c->seg_chk_d.reserve(slots * 256 * sizeof(float)))) return r;
-    seg = {c->seg_first.as<int>(), c->seg_extra.as<int2>(), reinterpret_cast<int *>(c->seg_extra.as<int2>() + want),
-           c->seg_chk.as<float4>(), c->image.as<float>(), (int)want, d_slot + 2, nullptr, my_tag};
+    seg = backward_segments(c, (int)want);
+    seg.asked = d_slot + 2;
+    seg.tag = my_tag;
   }
   // the tiles' largest stop indices of this forward, for the next one's decision below
   const bool figures = !gs_no_fwd_segments() && c->last_longest > gs::kSegSplitMin && num_tiles <= 16384;
   if (figures) seg.stats = d_slot;
   // ... and for the forward itself (gs_render.h: FwdSegments): every segment of a long list a block of its own, only
   // where the tiles' work is uneven enough
-  gs::FwdSegments fs = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, my_tag, nullptr, 0, 0};
+  gs::FwdSegments fs = {};
   const double gate = c->fseg_gate >= 0.0 ? c->fseg_gate : gs_fwd_segments_gate();
   const bool fsplit = figures && gs::forward_split_pays(c->fig.max, c->fig.sum, gate);
   if (fsplit) {
@@ -2341,30 +2332,37 @@ static int queue_sparse_tail(gsplat_context *c, FwdCall &f, size_t cap, long lon
       c->fseg_gran_zeroed_bytes = c->fseg_gran.bytes;
     }
     if (++c->fseg_epoch == 0) c->fseg_epoch = 1;
-    fs = {c->fseg_first.as<int>(), c->fseg_first.as<int>() + num_tiles + 8, c->fseg_blocks.as<int2>(),
-          reinterpret_cast<int *>(c->fseg_blocks.as<int2>() + want),
-          c->fseg_gran.as<unsigned long long>(), c->fseg_part.as<float4>(), c->fseg_stop.as<int>(), (int)want,
-          c->fseg_epoch, d_slot + 3, my_tag, c->fseg_fallbacks(), c->fseg_poll_budget, c->fseg_thin_layer};
+    fs.rank = c->fseg_first.as<int>();
+    fs.base = fs.rank + num_tiles + 8;
+    fs.blocks = c->fseg_blocks.as<int2>();
+    fs.count = reinterpret_cast<int *>(fs.blocks + want);
+    fs.granules = c->fseg_gran.as<unsigned long long>();
+    fs.part = c->fseg_part.as<float4>();
+    fs.stop = c->fseg_stop.as<int>();
+    fs.cap = (int)want;
+    fs.epoch = c->fseg_epoch;
+    fs.asked = d_slot + 3;
+    fs.tag = my_tag;
+    fs.fallbacks = c->fseg_fallbacks();
+    fs.poll_budget = c->fseg_poll_budget;
+    fs.thin_layer = c->fseg_thin_layer;
     if ((r = gs::launch_fwd_segments_table(c->ranges.as<int>(), num_tiles, fs, st))) return r;
     f.segmented_this_forward = true;  // (counted once per forward: a redone tail comes through here twice)
   }
   if (f.join_pending) GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));  // (late join: the records' colour is first read here)
-  gs::DepthMaps dm = f.dmap;
+  gs::RenderFwdArgs a = packed_forward_args(c, f, (long long)f.N * 4);  // M <= N is not known here yet
   if (c->depth) {
-    dm.chk = split ? c->seg_chk_d.as<float>() : nullptr;
-    dm.part = fsplit ? c->fseg_part_d.as<float>() : nullptr;
+    a.depth.chk = split ? c->seg_chk_d.as<float>() : nullptr;
+    a.depth.part = fsplit ? c->fseg_part_d.as<float>() : nullptr;
   }
   // Compact lists for the backward (gs_render.h: CompactLists): the one-workgroup-per-tile forward of a training context
   // writes them; a context that has seen a list beyond kSegSplitMin keeps the segment paths as they are.
   const bool compact = !ro && c->compact_lists && !gs_no_compact_lists() && !split && !figures && !fsplit;
-  const gs::CompactLists cl = {c->ids_c.as<int>(), c->masks_c.as<unsigned short>(), c->n_c_px.as<int>(), c->tile_useful.as<int>()};
-  r = gs::launch_render_fwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(), f.W, f.H, f.bg,
-                            c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
-                            c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)f.N * 4,  // M <= N is not known here yet
-                            ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr,
-                            (ordered || split || figures) ? c->tile_tops.as<int>() : nullptr, split ? &seg : nullptr,
-                            fsplit ? &fs : nullptr, c->depth ? &dm : nullptr, compact ? &cl : nullptr);
-  if (r) return r;
+  if (ordered || split || figures) a.tops_out = c->tile_tops.as<int>();
+  if (split) a.segments = seg;  // (without a split the kernel sees none of seg: its tag and stats are launch_tile_segments')
+  a.fwd_segments = fs;
+  if (compact) a.compact = compact_lists(c);
+  if ((r = gs::launch_render_fwd(a, st))) return r;
   c->compact_written = compact;
   c->seg_ready = split;
   c->seg_cap = seg.extra_cap;
@@ -2429,12 +2427,7 @@ static int finish_radix_route(gsplat_context *c, const FwdCall &f, const gs::For
   c->mark(4, false, st);
   if (f.join_pending) GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));
   // (no tile order on this route: the longest list is not known; see queue_sparse_tail)
-  rc = gs::launch_render_fwd(c->recs.as<float4>(), nullptr, c->sorted.as<int>(), c->ranges.as<int>(), f.W, f.H, f.bg,
-                             c->n_px.as<int>(), c->T_px.as<float>(), c->image.as<float>(), st,
-                             c->rows_zeroed ? c->grad_rows.as<float4>() : nullptr, (long long)rec.M * 4,
-                             f.ro ? nullptr : c->blockmasks.as<unsigned short>(), nullptr, nullptr, nullptr, nullptr,
-                             c->depth ? &f.dmap : nullptr, nullptr);
-  if (rc) return rc;
+  if ((rc = gs::launch_render_fwd(packed_forward_args(c, f, (long long)rec.M * 4), st))) return rc;
   c->compact_written = false;  // (the longest list is not known on this route: its backwards walk the full lists)
   c->seg_ready = false;
   c->mark(4, true, st);
@@ -2592,24 +2585,31 @@ int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, con
   c->rows_zeroed = false;
   // stage 6 is this one launch: when it is timed, the launch itself stamps the two events (see launch_render_bwd)
   const bool timed = (c->timing >> 6) & 1u;
-  gs::TileSegments seg = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0u};
-  if (c->seg_ready)
-    seg = {c->seg_first.as<int>(), c->seg_extra.as<int2>(), reinterpret_cast<int *>(c->seg_extra.as<int2>() + c->seg_cap),
-           c->seg_chk.as<float4>(), c->image.as<float>(), c->seg_cap, nullptr, nullptr, 0u};
-  gs::DepthMaps dm = {};
-  if (depth)
-    dm = {c->xyz_c.as<float>(), c->depth_map.as<float>(), nullptr, c->seg_ready ? c->seg_chk_d.as<float>() : nullptr,
-          grad_depth, grad_alpha};
+  gs::RenderBwdArgs a = {};
+  a.recs = c->recs.as<float4>();
   // compact lists (gs_render.h: CompactLists): the same kernel on the useful entries only -- ids, masks and stop indices
   const bool compact = c->compact_ready && !c->seg_ready;
-  int rc = gs::launch_render_bwd(c->recs.as<float4>(), nullptr, compact ? c->ids_c.as<int>() : c->sorted.as<int>(),
-                                 c->ranges.as<int>(), compact ? c->n_c_px.as<int>() : c->n_px.as<int>(),
-                                 c->T_px.as<float>(), grad_image, W, H, bg_color,
-                                 c->grad_rows.as<float>(), nullptr, nullptr, nullptr, nullptr, st,
-                                 compact ? c->masks_c.as<unsigned short>() : c->blockmasks.as<unsigned short>(), timed ? c->ev[c->slot][12] : nullptr,
-                                 timed ? c->ev[c->slot][13] : nullptr,
-                                 (c->order_ready && !gs_no_tile_order()) ? c->tile_order.as<int>() : nullptr,
-                                 c->seg_ready ? &seg : nullptr, depth ? &dm : nullptr, c->absgrad);
+  const gs::CompactLists cl = compact_lists(c);
+  a.sorted = compact ? cl.ids : c->sorted.as<int>();
+  a.masks_in = compact ? cl.masks : c->blockmasks.as<unsigned short>();
+  a.n_px = compact ? cl.n_px : c->n_px.as<int>();
+  a.ranges = c->ranges.as<int>();
+  a.T_px = c->T_px.as<float>();
+  a.grad_image = grad_image;
+  a.width = W; a.height = H; a.bg = bg_color;
+  a.out.rows = c->grad_rows.as<float>();
+  if (c->order_ready && !gs_no_tile_order()) a.order = c->tile_order.as<int>();
+  if (timed) { a.ev_start = c->ev[c->slot][12]; a.ev_stop = c->ev[c->slot][13]; }
+  if (c->seg_ready) a.segments = backward_segments(c, c->seg_cap);
+  if (depth) {
+    a.depth.xyz_c = c->xyz_c.as<float>();
+    a.depth.depth = c->depth_map.as<float>();
+    if (c->seg_ready) a.depth.chk = c->seg_chk_d.as<float>();
+    a.depth.grad_depth = grad_depth;
+    a.depth.grad_alpha = grad_alpha;
+  }
+  a.absgrad = c->absgrad;
+  const int rc = gs::launch_render_bwd(a, st);
   if (rc) return rc;
   if (c->seg_ready) c->n_segmented_backwards++;
   if (compact) c->n_compact_backwards++;
@@ -2862,7 +2862,8 @@ static int backward_pass(const char *fn, gsplat_context *c, const gsplat_gaussia
   }
   if (out && (rc = check_gradient_arrays(fn, out, l_max))) return rc;
   // (the compositing half checks its own arguments before its first launch)
-  rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, nullptr, nullptr, nullptr, stream);
+  rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, /*rgb_global=*/nullptr,
+                                    /*common=*/nullptr, /*uv_norm=*/nullptr, stream);
   if (rc) return rc;
   return backward_gaussians_impl(fn, c, g, cam, l_max, out, nullptr, nullptr, 0, g->num_gaussians, stream, nullptr, 2,
                                  grad_view, grad_campos);

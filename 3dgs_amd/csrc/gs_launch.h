@@ -1,0 +1,59 @@
+// gs_launch.h -- the host functions one .hip file of the library defines and another calls, declared once.  The files
+// that define them include this header too, so callers and definitions read one text: there is no second copy of a
+// prototype to fall behind (a definition whose parameters drift is, to C++, a new overload -- the linker still has the
+// last word on that, but the declaration to look at is this one).
+#pragma once
+#include "gs_common.h"
+
+namespace gs {
+
+struct TileSegments;  // gs_render.h
+struct FwdSegments;
+struct RenderFwdArgs;
+struct RenderBwdArgs;
+
+// ---- gs_binning.hip
+size_t binning_temp_bytes(size_t N, size_t S, int num_tiles);
+int scan_counts(int N, const int *counts, int *offsets, void *temp, size_t temp_bytes, hipStream_t st);
+bool binning_supports_counting_sort(int num_tiles);
+bool binning_prefers_radix(size_t S, int num_tiles);
+bool binning_next_route_is_radix(bool was_counting_sort, size_t S, int num_tiles, long long longest);
+size_t binning_table_bytes(int num_tiles);
+int binning_offsets(int ntx, int nty, int *table, int *long_tiles, hipStream_t st);
+int binning_scatter_and_sort(const float *uv, const float *xyz_c, const float *radius,
+                             const unsigned long long *hitmask, const int *rank, int N, int ntx, int nty,
+                             const int *table, int *ranges, size_t S, unsigned long long *payload,
+                             int *long_tiles, int *sorted_out, long long longest, const int *m_total,
+                             const unsigned long long *pair_counters, unsigned long long *pub,
+                             unsigned long long ticket, hipStream_t st, const SortFork *fork, bool compact_walk,
+                             bool keys_ok);
+int emit_sort_ranges(const float *uv, const float *xyz_c, const float *radius, int ntx, int nty, int N,
+                     const unsigned char *mask, const int *rank, const int *offsets, size_t S, unsigned int *tkeys_a,
+                     unsigned int *tkeys_b, unsigned long long *pay_a, unsigned long long *pay_b, int *sorted_out,
+                     int *ranges, void *temp, size_t temp_bytes, hipStream_t st, bool already_emitted,
+                     const unsigned long long *hitmask);
+int launch_tile_emit(const float *uv, const float *xyz_c, const float *radius, int ntx, int nty, int N,
+                     const unsigned char *mask, const int *rank, const int *offsets,
+                     const unsigned long long *hitmask, long long capacity, unsigned int *tkeys,
+                     unsigned long long *payload, hipStream_t st);
+
+// ---- gs_render.hip.  The two compositing launchers take their arguments by name (gs_render.h: RenderFwdArgs,
+// RenderBwdArgs).  launch_render_bwd stamps ev_start / ev_stop from the dispatch itself when both are given, whichever
+// kernel it selects (until the argument structs only the packed-records-and-rows forms did; no caller times another).
+int launch_render_fwd(const RenderFwdArgs &a, hipStream_t st);
+int launch_render_bwd(const RenderBwdArgs &a, hipStream_t st);
+int launch_fwd_segments_table(const int *ranges, int num_tiles, const FwdSegments &fs, hipStream_t st);
+int launch_tile_segments(const int *ranges, const int *tops, int num_tiles, const TileSegments &seg, hipStream_t st);
+int launch_contributions(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
+                         int width, int height, float *weight_sum, float *weight_max, int *pixels, hipStream_t st);
+int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
+bool tile_order_supported(int num_tiles);
+
+// ---- gs_filter3d.hip: the 3D smoothing filter's parameter transform and its chain rule (gsplat_context_set_filter3d)
+int launch_filter3d_apply(const float *scale, const float *opacity, const float *filter3d, int N, float *scale_eff,
+                          float *opacity_eff, hipStream_t st);
+int launch_filter3d_apply_bwd(const float *scale, const float *opacity, const float *filter3d, const int *rows, int M,
+                              float *grad_scale, int scale_stride, float *grad_opacity, int opacity_stride,
+                              bool at_gaussian, int first, int end, int span, hipStream_t st);
+
+}  // namespace gs

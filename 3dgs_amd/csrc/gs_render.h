@@ -633,4 +633,54 @@ struct CompactLists {
   int *count;             // [num_tiles]: useful entries the tile's workgroup ranked (all of them unless every pixel saturated)
 };
 
+struct RawSplats {  // the reference operator's input arrays
+  const float *uv, *opacity, *conic, *rgb;
+};
+struct GradOut {         // either whole rows ...
+  float *rows;           // [M,16]: rgb3 opacity1 conic3 uv2, 7 pad
+  // ... or the reference operator's four arrays
+  float *rgb, *opacity, *uv, *conic;
+};
+
+// ---- What the two compositing launchers take (gs_launch.h).  A caller starts from {} and assigns members by name; whatever
+// it leaves alone is off.  The option structs are held by value and a value-initialised one means "off", which is how the
+// kernels read them: TileSegments is on when chk is set, FwdSegments when blocks is, CompactLists when ids is, and
+// DepthMaps -- depth mode -- when xyz_c is.  The gaussians come as `recs` (the context's packed 48-byte records) or as
+// `raw` (the reference operator's arrays), never both.
+struct RenderFwdArgs {
+  const float4 *recs;
+  RawSplats raw;
+  const int *sorted, *ranges;  // the tile lists
+  int width, height;
+  float bg;
+  int *n_out;    // [H,W] per pixel: the stop index ...
+  float *T_out;  // ... the final transmittance ...
+  float *image;  // ... and the colour
+  float4 *zero;        // optional: `zero_vec` float4 the kernel clears on the side (the backward's gradient rows)
+  long long zero_vec;
+  unsigned short *masks_out;  // optional, per instance: the block masks, for the backward
+  int *tops_out;              // optional, per tile: the largest stop index of its pixels
+  TileSegments segments;      // the backward's checkpoints of long lists
+  FwdSegments fwd_segments;   // long lists as blocks of their own
+  DepthMaps depth;
+  CompactLists compact;       // the context's unsegmented forward only
+};
+struct RenderBwdArgs {
+  const float4 *recs;
+  RawSplats raw;
+  const int *sorted, *ranges;  // the tile lists (compact lists: their useful entries, with `masks_in` and `n_px` to match)
+  const int *n_px;             // [H,W] the forward's stop indices ...
+  const float *T_px;           // ... and final transmittances
+  const float *grad_image;
+  int width, height;
+  float bg;
+  GradOut out;                     // rows, or the four arrays
+  const unsigned short *masks_in;  // the forward's block masks (packed records only; the raw form computes them)
+  const int *order;                // optional: the tiles heaviest first (launch_tile_order)
+  hipEvent_t ev_start, ev_stop;    // optional, both or neither: the launch stamps them itself
+  TileSegments segments;
+  DepthMaps depth;  // depth mode: needs recs and out.rows
+  bool absgrad;     // likewise
+};
+
 }  // namespace gs

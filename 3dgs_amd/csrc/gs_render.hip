@@ -31,39 +31,28 @@
 //     to HBM as whole 64-byte gradient rows (or into the reference's four gradient arrays).
 #include <hip/hip_ext.h>
 #include "gs_common.h"
+#include "gs_launch.h"
 #include "gs_render.h"
 
 #include <cstdlib>
 #include <type_traits>
 
-#ifndef GS_ABLATE
-#define GS_ABLATE 0
-#endif
 // Diagnostic build (-DGS_STAMP=1, tools/bwd_timeline.py): every wave of render_bwd records where its cycles went
 // (s_memtime around the barriers, staging, list building, the trip loop and the flush) into a device array that
 // gsplat_debug_read_stamps copies out.  No stamp code exists in the normal build.
 #ifndef GS_STAMP
 #define GS_STAMP 0
 #endif
-#ifndef GS_EXTRA_FMA
-#define GS_EXTRA_FMA 0
-#endif
-// r04: the nine-value row reduction with two butterfly stages folded into the products (gs_render.h: 1 = row_moments9q,
-// 17 VALU + 1 wait state; 2 = row_moments9r, 14 VALU with the quad's constant cy factored out of three of the moments
-// and the atomic's address in the wait state) instead of one (0 = row_moments9, 22 + 3: the r01-r03 form; A/B: tools/ab).
-#ifndef GS_ROWSUM_QUAD
-#define GS_ROWSUM_QUAD 2
-#endif
-// r04 A/B switches of the backward's loop (profiles/r04_ab_*.txt): the exponent chain as one asm block; the issue priority
-// of the trip loop (0: none)
-#ifndef GS_BWD_ALPHA_ASM
-#define GS_BWD_ALPHA_ASM 1
-#endif
+// The backward's trip loop exists in ONE form.  What it was measured against, each once a build switch of this file
+// (profiles/README.md has the commands, for the commits that still had the switches):
+//   * the row reduction row_moments9r (gs_render.h: 14 VALU) against row_moments9q (17 + 1 wait state) and row_moments9
+//     (22 + 3, the r01-r03 form): launch 0.3440 -> 0.3261 -> 0.291 ms (profiles/r04_ab_rowsum.txt, r04_ab_carried_dot_...);
+//   * the exponent chain as one asm block against staged_alpha() + a separate FMA (an s_nop per asm border, three per trip);
+//   * the 0.99 cap as the forward's v_exp_f32(kLog2AlphaMax) against the literal 0.99f (profiles/r05_ab_backward_cap.txt);
+//   * r03's ablations and slope experiment (profiles/r03_valu_slope.txt; row reduction + LDS atomic removed: -134.3 us).
+// GS_BWD_PRIO: the issue priority of the trip loop (0: none), r04 A/B (profiles/r04_ab_*.txt)
 #ifndef GS_BWD_PRIO
 #define GS_BWD_PRIO 1
-#endif
-#ifndef GS_BWD_CAP_AS_FORWARD
-#define GS_BWD_CAP_AS_FORWARD 1
 #endif
 // r05: waves 2 and 3 -- idle while waves 0 and 1 staged a batch and while they run the flush's first step (124 slots
 // occupy two waves: 10 % of the kernel's wave cycles were waves 2 and 3 waiting at those two barriers) -- take the staging
@@ -105,10 +94,6 @@ namespace gs {
 #endif
 constexpr int kBatch = GS_FWD_BATCH;
 
-struct RawSplats {  // the reference operator's input arrays
-  const float *uv, *opacity, *conic, *rgb;
-};
-
 template <bool kPacked>
 __device__ __forceinline__ SplatRec load_record(int g, const float4 *__restrict__ recs, const RawSplats &raw) {
   if constexpr (kPacked) {
@@ -120,12 +105,6 @@ __device__ __forceinline__ SplatRec load_record(int g, const float4 *__restrict_
                        raw.opacity[g], raw.rgb[3 * g], raw.rgb[3 * g + 1], raw.rgb[3 * g + 2]);
   }
 }
-
-struct GradOut {         // either whole rows ...
-  float *rows;           // [M,16]: rgb3 opacity1 conic3 uv2, 7 pad
-  // ... or the reference operator's four arrays
-  float *rgb, *opacity, *uv, *conic;
-};
 
 constexpr int kListStride = kBatch;  // entries per row list (a batch can put all of its 256 slots on one list)
 
@@ -747,9 +726,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
                                                               const int *__restrict__ order, TileSegments seg,
                                                               DepthMaps dm) {
   static_assert(kPacked || !kDepth, "depth mode is a mode of the context's (packed) kernels");
-  static_assert(!kDepth || GS_ROWSUM_QUAD == 2, "the tenth sum rides in row_moments9r's colour register");
-  static_assert(!kAbs || (kPacked && kRows && GS_ROWSUM_QUAD == 2 && GS_BWD_ALPHA_ASM == 1),
-                "absgrad mode is a mode of the context's kernel in its default loop form (row slots 10 and 11)");
+  static_assert(!kAbs || (kPacked && kRows), "absgrad mode is a mode of the context's kernel (row slots 10 and 11)");
   __shared__ float4 s_r0[kB + 1], s_r1[kB + 1];  // [kB]: the all-zero sentinel record
   // [slot][9]: rgb, S0, Sx, Sy, Sxx, Sxy, Syy.  Doubles on purpose: on gfx950 ds_add_f32 retires about one LANE
   // every three cycles while ds_add_f64 runs at LDS rate (profiles/microbench/lds_atomic_rate: 109 vs 16 cycles for
@@ -871,20 +848,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
   if (top <= 0) { st_write(); return; }
 #endif
   if (top <= 0) return;
-  // where this lane's share of the nine row totals goes (see row_moments9), and the lane constants of the sums:
+  // where this lane's share of the nine row totals goes (see row_moments9r), and the lane constants of the sums:
   // pixel position relative to the tile centre, pixel gradient
-#if GS_ROWSUM_QUAD == 2
   // (depth mode: lane 3 of the row holds the tenth sum, aT x dL/d depth: the fourth channel of the colour register)
   const int red_idx = kDepth && (lane & 15) == 3 ? 9 : kAbs ? row_moments9r_abs_index(lane) : row_moments9r_index(lane);
-#elif GS_ROWSUM_QUAD
-  const int red_idx = row_moments9q_index(lane);
-#else
-  const int red_idx = row_moments9_index(lane);
-#endif
   const bool red_lane = red_idx >= 0;
-#if GS_BWD_CAP_AS_FORWARD
   const float alpha_cap = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, __builtin_amdgcn_exp2f(kLog2AlphaMax))));
-#endif
   const unsigned int acc_lane = (unsigned int)(size_t)(__attribute__((address_space(3))) char *)accb + (unsigned int)(red_idx * 8);
 
   // Split staging is for the fused path (packed 48-byte records: three loads that nothing touches until staging time).
@@ -948,12 +917,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
       if (t < count) {  // count <= kB
         const int g = sorted[start + base + t];
         SplatRec s = load_record<kPacked>(g, recs, raw);
-#if GS_ABLATE == 9
-        if constexpr (kPacked) {  // one more dependent global round trip: sensitivity to the staging latency
-          const float4 extra = recs[3 * (g ^ (int)(s.r0.x == 12345.678f)) + 1];
-          if (extra.x == 98765.4f) s.r0.x += 1.0f;
-        }
-#endif
         // the fused path hands over the forward's block masks; the raw-array operator computes them here
         if constexpr (kPacked) s.r2.w = __uint_as_float((unsigned int)masks_in[start + base + t]);
         else s.r2.w = __uint_as_float(block_hits(s, tx0, ty0));
@@ -988,18 +951,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
         gDb = gD;
         asm volatile("" : "+v"(gDb));
       }
-#if GS_ROWSUM_QUAD == 2
+      // (from the opaque index, like the addresses above: derived from the plain thread index the weights are
+      // loop-invariant for the whole kernel, get hoisted above the batch loop and spilled)
       const RowsWeights rw = make_rows_weights<kDepth>(t & 63, (float)(((t >> 6) & 1) * 8 + ((t >> 4) & 1) * 4 + (t & 3)) - 7.5f,
                                                        (float)((t >> 7) * 8 + ((t >> 5) & 1) * 4 + ((t >> 2) & 3)) - 7.5f, g0b, g1b, g2b, gDb);
-#elif GS_ROWSUM_QUAD
-      // (from the opaque index, like the addresses above: derived from the plain thread index the twelve weights are
-      // loop-invariant for the whole kernel, get hoisted above the batch loop and spilled)
-      const QuadWeights rw = make_quad_weights(t & 63, (float)(((t >> 6) & 1) * 8 + ((t >> 4) & 1) * 4 + (t & 3)) - 7.5f,
-                                               (float)((t >> 7) * 8 + ((t >> 5) & 1) * 4 + ((t >> 2) & 3)) - 7.5f, g0b, g1b, g2b);
-#else
-      const RowWeights rw = make_row_weights(lane, (float)((wave & 1) * 8 + (row & 1) * 4 + (j & 3)) - 7.5f,
-                                             (float)((wave >> 1) * 8 + (row >> 1) * 4 + (j >> 2)) - 7.5f, g0b, g1b, g2b);
-#endif
       // The loop is bound by VALU issue at the measured per-instruction costs (tools/valu_cost_model.py: compares,
       // selects and min/max cost 4.4 cycles per wave instruction against 2.9 for a multiply), so it exists twice: when
       // every pixel of the wave needs the whole batch (no pixel stopped inside it: the common case), the per-trip
@@ -1011,15 +966,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
           int off;
           asm volatile("ds_read_u16 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(off) : "v"(list_lds + 2 * i) : "memory");
           const float4 a = *reinterpret_cast<const float4 *>(r0b + off), b = *reinterpret_cast<const float4 *>(r1b + off);
-#if GS_ABLATE == 4
-          const float4 c = make_float4(0.5f, 0.25f, 0.125f, 0.0f);
-#else
           const float4 c = *reinterpret_cast<const float4 *>(r2b + off);
           asm volatile("" ::"v"(c.w));  // keep the 16-byte read: as ds_read_b96 it costs twice the LDS cycles (8 vs 4)
-#endif
           const float dx = a.x - fpx, dy = a.y - fpy;
           // opa * exp(power): d alpha / d gg . gg (the reference differentiates through the 0.99 cap as if absent)
-#if GS_BWD_ALPHA_ASM
           // The exponent chain of staged_alpha (the same operations in the same order: the forward's alpha bit for bit),
           // the exponential and -- in the wait state a transcendental's result needs before a plain VALU instruction may
           // read it -- the first FMA of the colour dot product, as ONE block: between separate asm statements the
@@ -1058,19 +1008,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
                 : [a2] "v"(a.z), [b2] "v"(a.w), [c2] "v"(b.x), [lopa] "v"(b.y), [dx] "v"(dx), [dy] "v"(dy), [cx] "v"(c.x),
                   [g0] "v"(g0), [s] "v"(s));
           }
-#else
-          float og = staged_alpha(a.z, a.w, b.x, b.y, dx, dy);  // opa * exp(power), before the 0.99 cap
-          const float t0 = __builtin_fmaf(c.x, g0, -s);
-#endif
-#if GS_EXTRA_FMA > 0
-          // slope experiment (tools/experiments/r03_valu_slope.sh): GS_EXTRA_FMA independent plain FMAs per trip whose
-          // results die at once -- pure issue slots, no new dependency, no live register
-#pragma unroll
-          for (int e = 0; e < GS_EXTRA_FMA; ++e) {
-            float sink;
-            asm volatile("v_fma_f32 %0, %1, %2, %3" : "=v"(sink) : "v"(dx), "v"(dy), "v"(a.z));
-          }
-#endif
           // a row past the end of its list reads the sentinel record (alpha 0).  n is 0 for pixels outside the image,
           // so "inside" needs no separate test.  The 1/255 floor is tested on og itself: min(0.99, og) >= 1/255 says the
           // same (written as "not below", so that a NaN passes as it does through the reference's fminf), and the cap is
@@ -1078,21 +1015,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
           // its full issue slot, tools/experiments/r03_valu_slope.sh).
           const bool valid = kCheckN ? (!(og < kAlphaMin) && (off < n_rel)) : !(og < kAlphaMin);
           if (__ballot(valid) == 0ull) continue;
-#if GS_ABLATE == 8
-          asm volatile("" ::"v"(og));
-          continue;
-#endif
           og = valid ? og : 0.0f;
           float alpha;  // fminf() would first canonicalise the selected value (a v_max_f32 og, og): the instruction saved
-#if GS_BWD_CAP_AS_FORWARD
           // the cap the FORWARD composed with: it folds min(0.99, .) into the exponent, so a capped alpha is
           // v_exp_f32(kLog2AlphaMax), two ulps below 0.99f -- rebuilding T with the exact 0.99f would drift from the
           // forward's T by 1.5e-5 relative per capped splat; the same value from the same instruction here
           asm("v_min_f32 %0, %2, %1" : "=v"(alpha) : "v"(og), "s"(alpha_cap));
-#else
-          asm("v_min_f32 %0, 0x3f7d70a4, %1" : "=v"(alpha) : "v"(og));  // min(0.99f, og), kAlphaMax
-          static_assert(kAlphaMax == 0.99f, "the literal above is 0.99f");
-#endif
           const float inv = __builtin_amdgcn_rcpf(1.0f - alpha);
           T *= inv;                                           // transmittance in front of this splat
           const float aT = alpha * T;
@@ -1105,32 +1033,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
           // nine raw sums: aT x pixel gradient (d/d rgb) and the six moments of gp about the tile centre; signs, the
           // -1/2 factors, (1 - opa), the shift to the gaussian's centre and 0.5*W / 0.5*H are applied once per gaussian
           // at flush time
-#if GS_ABLATE == 2
-          asm volatile("" ::"v"(aT), "v"(gp));
-#else
-#if GS_ROWSUM_QUAD == 2
           unsigned int acc_addr;
           float red;
           if constexpr (kAbs) red = row_moments9r_abs(aT, gp, pu, pv, rw, (unsigned int)off, acc_lane, acc_addr);
           else red = row_moments9r(aT, gp, rw, (unsigned int)off, acc_lane, acc_addr);
-#elif GS_ROWSUM_QUAD
-          const float red = row_moments9q(aT, gp, rw);
-          const unsigned int acc_addr = acc_lane + __umul24((unsigned int)off, 5u);
-#else
-          const float red = row_moments9(aT, gp, rw);
-          const unsigned int acc_addr = acc_lane + __umul24((unsigned int)off, 5u);
-#endif
-#if GS_ABLATE == 1
-          asm volatile("" ::"v"(red), "v"(acc_addr));
-#else
           // Every lane that holds a sum adds it, zero or not (a compare to skip zeros costs more issue cycles than the
           // few extra lanes cost the LDS; rows past their list add zeros to the sentinel slot's accumulators).  32-bit
           // LDS address on purpose: through a generic pointer the compiler forms off * 5 with a 64-bit multiply-add.
           if (red_lane)
             __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(3))) double *>(acc_addr),
                                    (double)red, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#endif
-#endif
         }
       };
       // The trip loop issues at a raised priority (r04): a SIMD's vector issue goes to the highest priority first, then
@@ -1202,10 +1114,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
         if (slot >= count) continue;
         const float val = s_res[slot * kRes + k];
         if (!(val != 0.0f)) continue;  // zero (nothing to add) -- NaN still goes out
-#if GS_ABLATE == 3
-        asm volatile("" ::"v"(val));
-        continue;
-#endif
         const int g = s_id[slot];
         if constexpr (kRows) {
           atomicAdd(&out.rows[(size_t)g * 16 + k], val);
@@ -1245,7 +1153,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
 #endif
 constexpr int kHalf = 62;
 static_assert(kSegEntries % kHalf == 0, "a segment is a whole number of half-batches");
-static_assert(GS_ROWSUM_QUAD == 2 && GS_BWD_ALPHA_ASM == 1 && GS_BWD_CAP_AS_FORWARD == 1, "the ping-pong kernel exists in the default loop form only");
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void render_bwd_pp_kernel(
     const float4 *__restrict__ recs, const int *__restrict__ sorted, const int *__restrict__ ranges, const int *__restrict__ n_px,
@@ -1999,100 +1906,69 @@ __global__ __launch_bounds__(256) void contributions_kernel(const float4 *__rest
   }
 }
 
-// host-side launchers shared with gs_fused.hip ------------------------------------------
-int launch_render_fwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, int width,
-                      int height, float bg, int *n_out, float *T_out, float *image, hipStream_t st, float4 *zero,
-                      long long zero_vec, unsigned short *masks_out, const int *order, int *tops_out, const TileSegments *segments,
-                      const FwdSegments *fwd_segments, const DepthMaps *depth, const CompactLists *compact) {
-  const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
-  const CompactLists cl = compact ? *compact : CompactLists{nullptr, nullptr, nullptr, nullptr};
-  GS_REQUIRE(!compact || (recs && !fwd_segments && !segments), "compact lists: the context's unsegmented forward only");
-  RawSplats none = {nullptr, nullptr, nullptr, nullptr};
-  const TileSegments seg = segments ? *segments : TileSegments{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
-  const FwdSegments fs = fwd_segments ? *fwd_segments : FwdSegments{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0};
-  const dim3 grid(tile_grid(num_tiles) + (fs.blocks ? fs.cap : 0)), block(256);
-  const DepthMaps dm = depth ? *depth : DepthMaps{};
-  GS_REQUIRE(recs || !depth, "depth mode needs the packed records");
-  if (recs && depth && compact) {
-    render_fwd_kernel<true, true, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm, cl);
-  } else if (recs && compact) {
-    render_fwd_kernel<true, false, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm, cl);
-  } else if (recs && depth) {
-    render_fwd_kernel<true, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm, cl);
-  } else if (recs) {
-    render_fwd_kernel<true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, masks_out, order, tops_out, seg, fs, dm, cl);
-  } else {
-    render_fwd_kernel<false><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, zero, zero_vec, nullptr, order, tops_out, seg, fs, dm, cl);
-  }
+// host-side launchers shared with gs_fused.hip (gs_launch.h) ------------------------------
+// One launch of `kernel`, its arguments converted to its parameter types.  With both events it is a timed launch (the
+// context's per-stage timing): the events take the begin and end timestamps of THIS dispatch from its completion signal.
+// Two hipEventRecord calls around the launch are barrier packets of their own and kept the GPU idle for ~11 us before and
+// ~6 us after the kernel in every step they were on.
+template <typename... P>
+static void launch_tiles(void (*kernel)(P...), dim3 grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop,
+                         std::common_type_t<P>... args) {
+  if (ev_start && ev_stop) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ev_start, ev_stop, 0, args...);
+  else kernel<<<grid, dim3(256), 0, st>>>(args...);
+}
+
+int launch_render_fwd(const RenderFwdArgs &a, hipStream_t st) {
+  const int ntx = (a.width + 15) / 16, nty = (a.height + 15) / 16, num_tiles = ntx * nty;
+  const TileSegments &seg = a.segments;
+  const FwdSegments &fs = a.fwd_segments;
+  const bool packed = a.recs != nullptr, depth = a.depth.xyz_c != nullptr, compact = a.compact.ids != nullptr;
+  GS_REQUIRE(!compact || (packed && !fs.blocks && !seg.chk), "compact lists: the context's unsegmented forward only");
+  GS_REQUIRE(packed || !depth, "depth mode needs the packed records");
+  const dim3 grid(tile_grid(num_tiles) + (fs.blocks ? fs.cap : 0));
+  auto launch = [&](auto kernel) {  // (order: the forward takes its tiles as they come)
+    launch_tiles(kernel, grid, st, nullptr, nullptr, a.recs, a.raw, a.sorted, a.ranges, a.width, a.height, ntx, num_tiles, a.bg,
+                 a.n_out, a.T_out, a.image, a.zero, a.zero_vec, a.masks_out, nullptr, a.tops_out, seg, fs, a.depth, a.compact);
+  };
+  if (compact) depth ? launch(render_fwd_kernel<true, true, true>) : launch(render_fwd_kernel<true, false, true>);
+  else if (packed) depth ? launch(render_fwd_kernel<true, true>) : launch(render_fwd_kernel<true>);
+  else launch(render_fwd_kernel<false>);
   GS_LAUNCH_CHECK();
   if (fs.blocks) {
-    if (depth)
-      fwd_segments_combine_kernel<true><<<num_tiles, 256, 0, st>>>(ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, tops_out, fs, seg, dm);
-    else
-      fwd_segments_combine_kernel<<<num_tiles, 256, 0, st>>>(ranges, width, height, ntx, num_tiles, bg, n_out, T_out, image, tops_out, fs, seg, dm);
+    auto combine = [&](auto kernel) {
+      kernel<<<num_tiles, 256, 0, st>>>(a.ranges, a.width, a.height, ntx, num_tiles, a.bg, a.n_out, a.T_out, a.image, a.tops_out, fs, seg, a.depth);
+    };
+    depth ? combine(fwd_segments_combine_kernel<true>) : combine(fwd_segments_combine_kernel<false>);
     GS_LAUNCH_CHECK();
   }
   return GSPLAT_OK;
 }
 
-int launch_render_bwd(const float4 *recs, const RawSplats *raw, const int *sorted, const int *ranges, const int *n_px,
-                      const float *T_px, const float *grad_image, int width, int height, float bg, float *rows,
-                      float *g_rgb, float *g_opacity, float *g_uv, float *g_conic, hipStream_t st, const unsigned short *masks_in,
-                      hipEvent_t ev_start, hipEvent_t ev_stop, const int *order, const TileSegments *segments,
-                      const DepthMaps *depth, bool absgrad) {
-  const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
-  const TileSegments seg = segments ? *segments : TileSegments{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+int launch_render_bwd(const RenderBwdArgs &a, hipStream_t st) {
+  const int ntx = (a.width + 15) / 16, nty = (a.height + 15) / 16, num_tiles = ntx * nty;
+  const TileSegments &seg = a.segments;
+  const bool packed = a.recs != nullptr, rows = a.out.rows != nullptr, depth = a.depth.xyz_c != nullptr;
+  GS_REQUIRE(!depth || (packed && rows), "depth mode needs the packed records and the gradient rows");
+  GS_REQUIRE(!a.absgrad || (packed && rows), "absgrad mode needs the packed records and the gradient rows");
   // split lists: their further segments are extra blocks in front of the main grid (blocks beyond the count leave at once)
-  const dim3 grid(tile_grid(num_tiles) + (seg.chk ? seg.extra_cap : 0)), block(256);
-  RawSplats none = {nullptr, nullptr, nullptr, nullptr};
-  GradOut out = {rows, g_rgb, g_opacity, g_uv, g_conic};
+  const dim3 grid(tile_grid(num_tiles) + (seg.chk ? seg.extra_cap : 0));
   const char *pp_env = getenv("GSPLAT_BWD_PINGPONG");  // (read per launch: the tests switch it inside one process)
   const int pingpong = pp_env ? atoi(pp_env) : GS_BWD_PINGPONG;
-  const DepthMaps dm = depth ? *depth : DepthMaps{};
-  GS_REQUIRE(!depth || (recs && rows), "depth mode needs the packed records and the gradient rows");
-  GS_REQUIRE(!absgrad || (recs && rows), "absgrad mode needs the packed records and the gradient rows");
-  if (absgrad) {  // (gs_render.h: row_moments9r_abs; like depth mode always the default loop, with or without depth gradients)
-#define GS_ABS_LAUNCH(DEPTH)                                                                                              \
-  do {                                                                                                                    \
-    if (ev_start && ev_stop)                                                                                              \
-      hipExtLaunchKernelGGL((render_bwd_kernel<true, true, GS_BWD_BATCH, DEPTH, true>), grid, block, 0, st, ev_start, ev_stop, \
-                            0, recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out,  \
-                            masks_in, order, seg, dm);                                                                     \
-    else                                                                                                                  \
-      render_bwd_kernel<true, true, GS_BWD_BATCH, DEPTH, true><<<grid, block, 0, st>>>(                                    \
-          recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm); \
-  } while (0)
-    if (depth) GS_ABS_LAUNCH(true);
-    else GS_ABS_LAUNCH(false);
-#undef GS_ABS_LAUNCH
-  } else if (depth) {  // (gs_render.h: DepthMaps; the ping-pong experiment has no depth form: always the default loop)
-    if (ev_start && ev_stop)
-      hipExtLaunchKernelGGL((render_bwd_kernel<true, true, GS_BWD_BATCH, true>), grid, block, 0, st, ev_start, ev_stop, 0, recs,
-                            none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order,
-                            seg, dm);
-    else
-      render_bwd_kernel<true, true, GS_BWD_BATCH, true><<<grid, block, 0, st>>>(recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
-  } else if (recs && rows && pingpong) {  // r06 experiment: two half-batches in flight (render_bwd_pp_kernel)
-    if (ev_start && ev_stop)
-      hipExtLaunchKernelGGL(render_bwd_pp_kernel, grid, block, 0, st, ev_start, ev_stop, 0, recs, sorted, ranges, n_px, T_px,
-                            grad_image, width, height, ntx, num_tiles, bg, rows, masks_in, order, seg);
-    else
-      render_bwd_pp_kernel<<<grid, block, 0, st>>>(recs, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, rows, masks_in, order, seg);
-  } else if (recs && rows && ev_start && ev_stop) {
-    // timed launch (the context's per-stage timing): the events take the begin and end timestamps of THIS dispatch from
-    // its completion signal.  Two hipEventRecord calls around the launch are barrier packets of their own and kept the
-    // GPU idle for ~11 us before and ~6 us after the kernel in every step they were on.
-    hipExtLaunchKernelGGL((render_bwd_kernel<true, true, GS_BWD_BATCH>), grid, block, 0, st, ev_start, ev_stop, 0, recs, none,
-                          sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
-  } else if (recs && rows) {
-    render_bwd_kernel<true, true, GS_BWD_BATCH><<<grid, block, 0, st>>>(recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
-  } else if (recs) {
-    render_bwd_kernel<true, false, GS_BWD_BATCH><<<grid, block, 0, st>>>(recs, none, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
-  } else if (rows) {  // the reference operator's input arrays, gradient rows out (gsplat_render_image_backward stages them)
-    render_bwd_kernel<false, true, GS_BWD_BATCH><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
-  } else {
-    render_bwd_kernel<false, false, GS_BWD_BATCH><<<grid, block, 0, st>>>(nullptr, *raw, sorted, ranges, n_px, T_px, grad_image, width, height, ntx, num_tiles, bg, out, masks_in, order, seg, dm);
-  }
+  auto launch = [&](auto kernel) {
+    launch_tiles(kernel, grid, st, a.ev_start, a.ev_stop, a.recs, a.raw, a.sorted, a.ranges, a.n_px, a.T_px, a.grad_image, a.width,
+                 a.height, ntx, num_tiles, a.bg, a.out, a.masks_in, a.order, seg, a.depth);
+  };
+  constexpr int kB = GS_BWD_BATCH;
+  // absgrad (gs_render.h: row_moments9r_abs) and depth mode (DepthMaps) are always the default loop: the ping-pong
+  // experiment (render_bwd_pp_kernel: two half-batches in flight) has neither form
+  if (a.absgrad) depth ? launch(render_bwd_kernel<true, true, kB, true, true>) : launch(render_bwd_kernel<true, true, kB, false, true>);
+  else if (depth) launch(render_bwd_kernel<true, true, kB, true>);
+  else if (packed && rows && pingpong)
+    launch_tiles(render_bwd_pp_kernel, grid, st, a.ev_start, a.ev_stop, a.recs, a.sorted, a.ranges, a.n_px, a.T_px, a.grad_image,
+                 a.width, a.height, ntx, num_tiles, a.bg, a.out.rows, a.masks_in, a.order, seg);
+  else if (packed) rows ? launch(render_bwd_kernel<true, true, kB>) : launch(render_bwd_kernel<true, false, kB>);
+  // the reference operator's input arrays; gradient rows out when gsplat_render_image_backward stages them
+  else rows ? launch(render_bwd_kernel<false, true, kB>) : launch(render_bwd_kernel<false, false, kB>);
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;
 }
@@ -2131,10 +2007,12 @@ int gsplat_render_image(const float *uv, const float *opacity, const float *coni
   GS_REQUIRE_DEV(sorted_splats); GS_REQUIRE_DEV(splat_range_by_tile); GS_REQUIRE_DEV(splats_per_pixel);
   GS_REQUIRE_DEV(weight_per_pixel); GS_REQUIRE_DEV(image);
   GS_REQUIRE(image_width > 0 && image_height > 0, "image size must be positive");
-  gs::RawSplats raw = {uv, opacity, conic, rgb};
-  return gs::launch_render_fwd(nullptr, &raw, sorted_splats, splat_range_by_tile, image_width, image_height,
-                               background_opacity, splats_per_pixel, weight_per_pixel, image, (hipStream_t)stream, nullptr,
-                               0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  gs::RenderFwdArgs a = {};
+  a.raw.uv = uv; a.raw.opacity = opacity; a.raw.conic = conic; a.raw.rgb = rgb;
+  a.sorted = sorted_splats; a.ranges = splat_range_by_tile;
+  a.width = image_width; a.height = image_height; a.bg = background_opacity;
+  a.n_out = splats_per_pixel; a.T_out = weight_per_pixel; a.image = image;
+  return gs::launch_render_fwd(a, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -2186,7 +2064,11 @@ int gsplat_render_image_backward(const float *uvs, const float *opacity, const f
   GS_REQUIRE_DEV(final_weight_per_pixel); GS_REQUIRE_DEV(grad_image); GS_REQUIRE_DEV(grad_rgb);
   GS_REQUIRE_DEV(grad_opacity); GS_REQUIRE_DEV(grad_uv); GS_REQUIRE_DEV(grad_conic);
   GS_REQUIRE(image_width > 0 && image_height > 0, "image size must be positive");
-  gs::RawSplats raw = {uvs, opacity, conic, rgb};
+  gs::RenderBwdArgs a = {};
+  a.raw.uv = uvs; a.raw.opacity = opacity; a.raw.conic = conic; a.raw.rgb = rgb;
+  a.sorted = sorted_splats; a.ranges = splat_range_by_tile;
+  a.n_px = num_splats_per_pixel; a.T_px = final_weight_per_pixel; a.grad_image = grad_image;
+  a.width = image_width; a.height = image_height; a.bg = background_opacity;
   hipStream_t st = (hipStream_t)stream;
   // Nine float atomics per (gaussian, tile) into FOUR arrays are four 64-byte atomic requests at the memory side where
   // the fused path's 64-byte gradient row is one (MI355X_MICROARCH.md, global float atomics: ~1.3 TB/s of 64-byte
@@ -2212,18 +2094,15 @@ int gsplat_render_image_backward(const float *uvs, const float *opacity, const f
     int rc = rows.reserve((size_t)bound * 64);
     if (rc) return rc;
     GS_HIP(hipMemsetAsync(rows.ptr, 0, (size_t)bound * 64, st));
-    rc = gs::launch_render_bwd(nullptr, &raw, sorted_splats, splat_range_by_tile, num_splats_per_pixel,
-                               final_weight_per_pixel, grad_image, image_width, image_height, background_opacity,
-                               rows.as<float>(), nullptr, nullptr, nullptr, nullptr, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false);
-    if (rc) return rc;
+    a.out.rows = rows.as<float>();
+    if ((rc = gs::launch_render_bwd(a, st))) return rc;
     rows_to_arrays_kernel<<<gs::div_up(bound, 256), 256, 0, st>>>(rows.as<float4>(), bound, grad_rgb, grad_opacity, grad_uv,
                                                                   grad_conic);
     GS_LAUNCH_CHECK();
     return GSPLAT_OK;
   }
-  return gs::launch_render_bwd(nullptr, &raw, sorted_splats, splat_range_by_tile, num_splats_per_pixel,
-                               final_weight_per_pixel, grad_image, image_width, image_height, background_opacity,
-                               nullptr, grad_rgb, grad_opacity, grad_uv, grad_conic, st, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+  a.out.rgb = grad_rgb; a.out.opacity = grad_opacity; a.out.uv = grad_uv; a.out.conic = grad_conic;
+  return gs::launch_render_bwd(a, st);
 }
 
 }  // extern "C"

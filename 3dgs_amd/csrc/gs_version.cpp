@@ -9,6 +9,6 @@ const char *gsplat_source_hash(void) {
 #include "gs_source_hash.inc"
       ;
 }
-// the EXTRA compiler flags of a diagnostic / experiment build (GS_STAMP, GS_ABLATE, ...); empty for the product build
+// the EXTRA compiler flags of a diagnostic / experiment build (GS_STAMP, GS_BWD_BATCH, ...); empty for the product build
 const char *gsplat_build_flags(void) { return GS_BUILD_FLAGS; }
 }

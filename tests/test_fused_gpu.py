@@ -968,3 +968,57 @@ def test_forward_stops_where_the_pixels_saturate(gpu, scene):
     ctx.close()
     print(f"bigsplats: render_fwd {ms:.4f} ms")
     perf_check(ms < 0.1, f"render_fwd takes {ms:.4f} ms on the saturating workload (0.062 with the exit, 0.131 without)")
+
+
+@pytest.mark.parametrize("form", ["plain", "full_lists", "depth", "absgrad", "pingpong"])
+def test_timed_backward_is_the_same_backward(gpu, scene, monkeypatch, form):
+    """Timing stage 6 (render_backward) changes HOW the compositing backward is launched: the launch stamps the two events
+    itself instead of going out as a plain launch (gs_render.hip: launch_tiles).  Only the benchmark took that path.  Every
+    backward form the launcher can select -- plain on the compact lists, plain on the full lists, depth, absgrad, ping-pong
+    -- must give, timed, the gradients it gives untimed (rel 1e-4: the sums are atomic, as in
+    test_tile_order_changes_nothing), leave the forward's outputs the same bits, and report one launch with a time.
+    `small` at view 2: the oracle's longest tile list there is 140 entries, two backward batches of 124 -- the smallest
+    existing scene on which the batch loop and the split-staging prefetch run more than once."""
+    torch, raster = gpu, pkg("raster")
+    N, W, H, L, _ = scene.WORKLOADS["small"]
+    c = scene.CONFIG
+    dp = raster.device_params(scene.make_gaussians(N, W, H, L))
+    dc = raster.device_camera(scene.make_camera(W, H, 2))
+    gi = torch.as_tensor(scene.make_grad_image(W, H)).cuda()
+    if form == "pingpong":
+        monkeypatch.setenv("GSPLAT_BWD_PINGPONG", "1")
+    ctx = raster.RasterContext(N, W, H)
+    kw = {}
+    if form == "full_lists":
+        ctx.set_compact_lists(False)
+    elif form == "depth":
+        ctx.set_depth(True)
+        rng = np.random.default_rng(3)  # non-zero everywhere, as tests/test_depth_gpu.py: _maps
+        gd, ga = ((rng.uniform(0.2, 1.0, (H, W)) * rng.choice([-1.0, 1.0], (H, W)) / (W * H)).astype(np.float32) for _ in range(2))
+        kw = dict(grad_depth=torch.as_tensor(gd).cuda(), grad_alpha=torch.as_tensor(ga).cuda())
+    elif form == "absgrad":
+        ctx.set_absgrad(True)
+
+    def step():
+        fwd = ctx.rasterize_image(dp, dc, c, c["bg"], L)
+        out = {k: fwd[k].clone() for k in ("image", "T", "n")}
+        grads = ctx.alloc_gradients(fwd["num_culled"], L, intermediates=True)
+        for g in grads.values():
+            g.fill_(float("nan"))
+        ctx.backward_pass(dp, dc, gi, c["bg"], L, grads, **kw)
+        return out, grads
+
+    out0, g0 = step()
+    ctx.set_timing(True, stages=["render_backward"])
+    out1, g1 = step()
+    torch.cuda.synchronize()
+    ms, launches = ctx.get_timing()["render_backward"]
+    print(f"{form}: timed render_bwd {ms:.4f} ms, {launches} launch(es)")
+    assert launches == 1 and ms > 0.0, (ms, launches)
+    if form in ("plain", "full_lists"):  # the two differ in the lists the backward walks
+        assert ctx.counters()["compact_list_backwards"] == (2 if form == "plain" else 0)
+    for k in g0:
+        assert_grad_close(_np(g1[k]), _np(g0[k]), f"{form}, timed vs untimed: grad_{k}", rel=1e-4)
+    for k in out0:
+        assert torch.equal(out1[k], out0[k]), f"{form}: the forward's {k} differs between the two runs"
+    ctx.close()
