@@ -694,7 +694,7 @@ static long long dense_tile_threshold() {
 // ------------------------------------------------------------------------------------------------
 // Sparse-scene binning without a global sort.  The per-tile depth sort re-orders every list anyway, so the grouping
 // by tile does not have to be stable -- a counting sort with all atomics in LDS does it:
-//   count:       done by preprocess_kernel itself (gs_fused.hip): workgroup b counts the tiles its slice of the
+//   count:       done by preprocess_kernel itself (gs_preprocess.hip): workgroup b counts the tiles its slice of the
 //                gaussians hits in an LDS histogram while it runs the hit tests anyway (ds_add_u32 runs at LDS
 //                rate; the same count through L2 atomics would cost more than the radix sort) and writes its
 //                histogram row table[b][0..T);

@@ -56,7 +56,7 @@ int check_device_ptr(const void *p, const char *name, const char *fn);
     }                                                                                         \
   } while (0)
 
-// Counting-sort binning (gs_binning.hip) and the per-gaussian forward (gs_fused.hip) split the gaussians into the same
+// Counting-sort binning (gs_binning.hip) and the per-gaussian forward (gs_preprocess.hip) split the gaussians into the same
 // kBinBlocks contiguous slices: workgroup b of either kernel owns global indices [N*b/kBinBlocks, N*(b+1)/kBinBlocks).
 constexpr int kBinBlocks = 256, kBinThreads = 1024;
 // r03: the gaussians are dealt to those workgroups in CHUNKS of 64 consecutive entries (one wave trip), round robin:

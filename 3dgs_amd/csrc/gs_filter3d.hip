@@ -8,7 +8,7 @@
 //   o         = sigmoid(opacity) * sqrt(det Sigma / det Sigma_eff)
 // The filter does not depend on the camera a view is rendered from, so it is a parameter transform in front of the
 // forward (filter3d_apply) and a chain rule behind the per-gaussian backward (filter3d_apply_backward): the compositing
-// and per-gaussian kernels see ordinary parameters (gsplat_context_set_filter3d, gs_fused.hip).
+// and per-gaussian kernels see ordinary parameters (gsplat_context_set_filter3d: gs_context.hip; the calls: gs_fused.hip).
 // Everything is one thread per gaussian.
 #include "gs_common.h"
 #include "gs_launch.h"

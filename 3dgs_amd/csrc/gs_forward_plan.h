@@ -3,7 +3,7 @@
 // the counts were known has to be redone, whether tile order and the forward split pay, how much segment room to
 // reserve, which published figures may be trusted, and how the forward's host record is laid out.  Plain C++17 with no
 // HIP include, so that a host compiler builds it alone (tests/cpp/forward_plan_test.cpp); the launches, the atomic
-// loads and everything that touches a context stay in gs_fused.hip.
+// loads and everything that touches a context (gs_context.h) stay in gs_fused.hip.
 #pragma once
 #include <algorithm>
 #include <cstddef>

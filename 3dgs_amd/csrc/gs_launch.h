@@ -3,6 +3,8 @@
 // prototype to fall behind (a definition whose parameters drift is, to C++, a new overload -- the linker still has the
 // last word on that, but the declaration to look at is this one).
 #pragma once
+#include <type_traits>
+
 #include "gs_common.h"
 
 namespace gs {
@@ -11,6 +13,11 @@ struct TileSegments;  // gs_render.h
 struct FwdSegments;
 struct RenderFwdArgs;
 struct RenderBwdArgs;
+struct CullArgs;  // gs_pergaussian_args.h
+struct PreprocessArgs;
+struct ShColourArgs;
+struct PreprocessBwdArgs;
+struct ShAdamDirArgs;
 
 // ---- gs_binning.hip
 size_t binning_temp_bytes(size_t N, size_t S, int num_tiles);
@@ -55,5 +62,43 @@ int launch_filter3d_apply(const float *scale, const float *opacity, const float 
 int launch_filter3d_apply_bwd(const float *scale, const float *opacity, const float *filter3d, const int *rows, int M,
                               float *grad_scale, int scale_stride, float *grad_opacity, int opacity_stride,
                               bool at_gaussian, int first, int end, int span, hipStream_t st);
+
+// ---- gs_preprocess.hip: the per-gaussian forward.  Arguments by name (gs_pergaussian_args.h); each launcher selects its
+// kernel's instantiation from the form members and writes the kernel's argument list once.
+int launch_project_cull(const CullArgs &a, hipStream_t st);
+int launch_preprocess(const PreprocessArgs &a, hipStream_t st);  // form: (l_max, store_mid, compact, antialiased)
+// the two-kernel forward; the fork / join of the side-by-side form stays with the caller.  colour: 0 degree 0, formed by the
+// geometry kernel; 1 read from a.rgb, where sh_colour_kernel has left it; 2 written into the records by sh_colour_kernel
+int launch_sh_colour(const ShColourArgs &a, hipStream_t st);                         // form: (l_max 1..3, compact)
+int launch_preprocess_geom(const PreprocessArgs &a, int colour, hipStream_t st);    // form: (colour, store_mid, compact)
+size_t scan_counts_temp_bytes(size_t N);  // rocPRIM's exclusive scan over N + 1 counts (gs_binning.hip: scan_counts)
+int launch_publish_counts(const int *rank_total, const int *offsets_total, const unsigned long long *pair_counters,
+                          unsigned long long *pub, unsigned long long ticket, hipStream_t st);
+
+// ---- gs_preprocess_bwd.hip: the per-gaussian backward; launches cam_grad_finalize_kernel too when a.cam_rows is set
+int launch_preprocess_bwd(const PreprocessBwdArgs &a, hipStream_t st);
+int launch_sh_adam_dir(const ShAdamDirArgs &a, hipStream_t st);  // (l_max 1..3)
+
+// ---- gs_exchange.hip: the compositing backward's colour rows scattered to global order (gsplat_backward_render_depth)
+int launch_scatter_rgb_rows(const unsigned char *mask, const int *rank, int N, const float *rows, float *rgb_global,
+                            float *common, float *uv_norm, hipStream_t st);
+
+// ---- run-time switches as compile-time constants, for the launchers' dispatches: f is a generic lambda that names the
+// kernel's instantiation from the constant's type (decltype(x)::value) -- no macro, one argument list per kernel
+template <class F>
+void with_bool(bool b, F &&f) {
+  if (b) f(std::true_type{}); else f(std::false_type{});
+}
+// SH degree kLowest..3 (a degree outside the range takes 3, as the switch statements this replaces did)
+template <int kLowest, class F>
+void with_degree(int l_max, F &&f) {
+  static_assert(kLowest == 0 || kLowest == 1, "kernels exist from degree 0 or from degree 1");
+  if constexpr (kLowest == 0) {
+    if (l_max == 0) return f(std::integral_constant<int, 0>{});
+  }
+  if (l_max == 1) f(std::integral_constant<int, 1>{});
+  else if (l_max == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 3>{});
+}
 
 }  // namespace gs

@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void optimizer_sh_factored_kernel(int rows, co
 // r05: the colour groups (band 0 and the SH coefficients) of a W-VIEW step, from what the split exchange delivers: every
 // view's g_rgb[N,3] in global order + its camera position (rgb_all) and the number of views that saw a gaussian
 // (common[., 11]).  Phase 1, one thread per gaussian: grad[k][c] = sum_r g_rgb^r[c] Y_k(dir^r) exactly as
-// unpack_split_kernel (gs_fused.hip) forms it -- views in rank order, views with an all-zero g_rgb skipped, mul then add --
+// unpack_split_kernel (gs_exchange.hip) forms it -- views in rank order, views with an all-zero g_rgb skipped, mul then add --
 // W basis evaluations per gaussian, into the wave's LDS rows (odd pitch: a lane writing ITS row is conflict-free).
 // Phase 2, the wave streams over its 64 consecutive parameter rows as ONE linear span (the rows of rgb[N,3] and of
 // sh[N,3(n-1)] are contiguous in global order): parameter and both moments are read and written coalesced, the gradient

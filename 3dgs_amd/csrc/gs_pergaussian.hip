@@ -1,6 +1,6 @@
 // gs_pergaussian.hip -- the stand-alone per-gaussian operators of the drop-in surface
 // (one thread per gaussian, wave64, 256-thread workgroups).  The math lives in gs_math.h
-// and is shared bit-for-bit with the fused preprocess kernels in gs_fused.hip.
+// and is shared bit-for-bit with the fused preprocess kernels in gs_preprocess.hip / gs_preprocess_bwd.hip.
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 

@@ -1,5 +1,5 @@
 // gs_render.h -- device helpers shared by the compositing kernels (gs_render.hip) and the
-// fused preprocess kernel (gs_fused.hip): the 48-byte "splat record" a tile stages in LDS,
+// fused preprocess kernel (gs_preprocess.hip): the 48-byte "splat record" a tile stages in LDS,
 // wave64 cross-lane reductions on DPP, and the XCD-aware block -> tile map.
 #pragma once
 #include <hip/hip_runtime.h>

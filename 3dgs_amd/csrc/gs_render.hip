@@ -1906,7 +1906,7 @@ __global__ __launch_bounds__(256) void contributions_kernel(const float4 *__rest
   }
 }
 
-// host-side launchers shared with gs_fused.hip (gs_launch.h) ------------------------------
+// host-side launchers called from gs_fused.hip (gs_launch.h) ------------------------------
 // One launch of `kernel`, its arguments converted to its parameter types.  With both events it is a timed launch (the
 // context's per-stage timing): the events take the begin and end timestamps of THIS dispatch from its completion signal.
 // Two hipEventRecord calls around the launch are barrier packets of their own and kept the GPU idle for ~11 us before and

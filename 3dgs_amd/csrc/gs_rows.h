@@ -1,5 +1,5 @@
-// gs_rows.h -- array-of-rows data between global memory and LDS (shared by the fused per-gaussian backward in
-// gs_fused.hip and the stand-alone spherical-harmonics backward in gs_pergaussian.hip).
+// gs_rows.h -- array-of-rows data between global memory and LDS (shared by the fused per-gaussian kernels in
+// gs_preprocess.hip / gs_preprocess_bwd.hip and the stand-alone spherical-harmonics backward in gs_pergaussian.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

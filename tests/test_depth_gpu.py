@@ -199,6 +199,49 @@ def test_every_per_gaussian_entry_point_takes_the_depth_term(gpu, scene, orc):
     assert torch.equal(oa.uv_grad_accum, ob.uv_grad_accum)
 
 
+@pytest.mark.parametrize("mode", [0, 1])
+def test_adam_forms_take_the_depth_term(gpu, scene, orc, mode):
+    """The other two Adam-inside forms behind gsplat_backward_render_depth (struct modes 0 and 1: preprocess_bwd_kernel's
+    kAdam 2 and 1 with kDepthRow; mode 2 is in the test above), on the 200-gaussian 64x48 `tiny` scene (four waves of
+    compacted slots, the last one partial).  The gradient arrays the call stores meet the float32 oracle's chain with
+    dL/d depth and dL/d alpha composed in at conftest's bars, and parameters, moments and statistics are those of the
+    plain depth backward + the unfused optimizer step, bit for bit."""
+    torch, opt_mod = gpu, pkg("optimizer")
+    N, W, H, L = scene.WORKLOADS["tiny"][:4]
+    raster, params, cam, dp, dc = _case(torch, scene, N, W, H, L, view=1)
+    c = scene.CONFIG
+    ctx = raster.RasterContext(N, W, H)
+    ctx.set_depth(True)
+    gi = scene.make_grad_image(W, H)
+    gd, ga, gd_d, ga_d = _maps(torch, W, H)
+    fwd = ctx.rasterize_image(dp, dc, c, c["bg"], L)
+    M = fwd["num_culled"]
+    assert M > 128  # more than two waves
+    ctx.backward_render(torch.as_tensor(gi).cuda(), c["bg"], grad_depth=gd_d, grad_alpha=ga_d)
+    dp_b = {k: v.clone() for k, v in dp.items()}
+    oa, ob = opt_mod.AdamOptimizer(dp, L, scene_extent=2.5), opt_mod.AdamOptimizer(dp_b, L, scene_extent=2.5)
+    g_a = ctx.alloc_gradients(M, L, intermediates=True, factored_sh=True)
+    g_b = ctx.alloc_gradients(M, L, intermediates=True, factored_sh=True)
+    for t in g_b.values():
+        if t is not None:
+            t.fill_(float("nan"))
+    ctx.backward_gaussians(dp, dc, L, g_a)
+    oa.step(1, fwd, g_a, campos=cam["campos"])
+    ctx.backward_gaussians_adam(dp_b, dc, L, ob.fused_state(1, mode=mode), g_b)
+    if mode == 1:  # the SH and the position group behind the kernel
+        ob.step_after_partial_backward(1, fwd, g_b, cam["campos"])
+    torch.cuda.synchronize()
+    ref = orc.rasterize(params, cam, c["near_thresh"], c["mh_dist"], c["cull_mask_padding"], c["bg"], L, threads=8)
+    g = depth_reference.backward_pass(orc, ref, cam, gi, gd, ga, c["bg"], L, threads=8)
+    _check_grads({k: v for k, v in g_b.items() if v is not None}, g)
+    no_depth = depth_reference.backward_pass(orc, ref, cam, gi, None, None, c["bg"], L, threads=8)
+    assert np.abs(np.asarray(g["xyz"]) - np.asarray(no_depth["xyz"])).max() > 0  # the depth term is part of what is checked
+    for k in oa.names:
+        assert torch.equal(dp[k], dp_b[k]), k
+        assert torch.equal(oa.exp_avg[k], ob.exp_avg[k]) and torch.equal(oa.exp_avg_sq[k], ob.exp_avg_sq[k]), k
+    assert torch.equal(oa.uv_grad_accum, ob.uv_grad_accum) and torch.equal(oa.grad_accum_dur, ob.grad_accum_dur)
+
+
 def _long_list_scene(scene):
     N, W, H, L = 24000, 160, 96, 1
     params = scene.make_gaussians(N, W, H, L)

@@ -21,7 +21,7 @@ def _free_port():
 
 
 def _pack_cpu(bwd, mask, l_max):
-    """numpy restatement of gsplat_pack_gradients_global (csrc/gs_fused.hip pack_global_kernel)."""
+    """numpy restatement of gsplat_pack_gradients_global (csrc/gs_exchange.hip pack_global_kernel)."""
     gdist = pkg("dist")
     cols, width = gdist.packed_layout(l_max)
     N = len(mask)

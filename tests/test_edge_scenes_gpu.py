@@ -262,7 +262,7 @@ def test_edge_backward_split_and_ranges_equal_the_whole(gpu, edge):
     for k in whole:
         assert torch.equal(whole[k][:M], parts[k][:M]), f"grad_{k}: ranges differ from the whole backward"
     _check_backward({k: whole[k][:M] for k in whole}, edge["bref"])
-    # common[i] = {xyz 3, opacity, scale 3, quaternion 4, visible} at the global index i (gs_fused.hip)
+    # common[i] = {xyz 3, opacity, scale 3, quaternion 4, visible} at the global index i (gs_preprocess_bwd.hip: BwdOut)
     common = torch.full((N, 12), float("nan"), device="cuda")
     ctx.backward_gaussians_split(dp, dc, L, common)
     torch.cuda.synchronize()
