@@ -214,6 +214,13 @@ SIGNATURES = {
     "gsplat_backward_render_depth": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _P]),
     "gsplat_backward_pass_depth": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _P, _P, _P, _F, _I,
                                         ctypes.POINTER(Gradients), _P]),
+    "gsplat_context_set_depth_mode": (_I, [_P, _I, _I]),
+    "gsplat_context_depth_moment_map": (_I, [_P, ctypes.POINTER(_P)]),
+    "gsplat_backward_render_depth2": (_I, [_P, _P, _P, _P, _P, _F, _P, _P, _P, _P]),
+    "gsplat_backward_pass_depth2": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _P, _P, _P, _P, _F, _I,
+                                         ctypes.POINTER(Gradients), _P]),
+    "gsplat_distortion_loss": (_I, [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P]),
+    "gsplat_depth_prior_loss": (_I, [_P, _P, _I, _I, _F, _I, _P, _P, _P]),
     "gsplat_backward_gaussians_camera": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _I,
                                               ctypes.POINTER(Gradients), _P, _P, _P]),
     "gsplat_backward_pass_camera": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _P, _P, _P, _F, _I,

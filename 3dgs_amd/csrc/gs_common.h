@@ -129,6 +129,7 @@ void pool_unwatch(const unsigned char **slot);
 enum ScratchSlot {
   SCR_COUNTS = 0, SCR_OFFSETS, SCR_KEYS_A, SCR_KEYS_B, SCR_VALS_B, SCR_TEMP, SCR_SPLATS, SCR_MISC, SCR_GRADROWS,
   SCR_LOSS_MU, SCR_LOSS_S1, SCR_LOSS_S12, SCR_LOSS_ACC,
+  SCR_DEPTH_LOSS,  // gsplat_distortion_loss / gsplat_depth_prior_loss: the blocks' partial sums (doubles)
   SCR_NUM
 };
 DeviceBuffer &scratch(ScratchSlot slot);

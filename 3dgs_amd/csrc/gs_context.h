@@ -65,6 +65,11 @@ struct gsplat_context {
   bool depth_ready = false;  // the recorded forward rendered depth_map
   bool rows_depth = false;   // the gradient rows carry dL/dz in slot 9 (gsplat_backward_render_depth with depth gradients)
   gs::DeviceBuffer depth_map, seg_chk_d, fseg_part_d;
+  // the mode's options (gsplat_context_set_depth_mode; gs_render.h: DepthMaps): s = 1/z, and the second moment Q with its
+  // side arrays.  The *_ready pair: what the recorded forward ran with (its backwards follow it, whatever is set by then)
+  bool depth_inverse = false, depth_moment = false;
+  bool depth_inverse_ready = false, depth_moment_ready = false;
+  gs::DeviceBuffer depth2_map, seg_chk_q, fseg_part_q;
   // absgrad mode (gsplat_context_set_absgrad): the compositing backward also sums every pixel's share of dL/d uv by absolute
   // value, into row slots 10 and 11 (gs_render.h: row_moments9r_abs); the densification statistics are made of those
   bool absgrad = false;
@@ -173,6 +178,7 @@ struct gsplat_context {
     f(c.seg_first, W); f(c.seg_extra, W); f(c.seg_chk, W);
     f(c.fseg_first, W); f(c.fseg_blocks, W); f(c.fseg_gran, W); f(c.fseg_part, W); f(c.fseg_stop, W);
     f(c.dir_grad, W); f(c.cam_rows, W); f(c.depth_map, W); f(c.seg_chk_d, W); f(c.fseg_part_d, W);
+    f(c.depth2_map, W); f(c.seg_chk_q, W); f(c.fseg_part_q, W);
     f(c.f3d_scale, W); f(c.f3d_opacity, W);
     f(c.chunk_first, 0u);  // released, not counted: as before this table
   }

@@ -170,6 +170,15 @@ int gsplat_context_detach_forward_outputs(gsplat_context *c) {
 int gsplat_context_set_depth(gsplat_context *c, int enabled) {
   GS_REQUIRE(c != nullptr, "null context");
   c->depth = enabled != 0;
+  c->depth_inverse = c->depth_moment = false;  // (the options are gsplat_context_set_depth_mode's)
+  return GSPLAT_OK;
+}
+
+int gsplat_context_set_depth_mode(gsplat_context *c, int inverse, int moment) {
+  GS_REQUIRE(c != nullptr, "null context");
+  c->depth = true;
+  c->depth_inverse = inverse != 0;
+  c->depth_moment = moment != 0;
   return GSPLAT_OK;
 }
 
@@ -218,6 +227,15 @@ int gsplat_context_depth_map(gsplat_context *c, const float **depth) {
   *depth = nullptr;
   GS_REQUIRE(c->n_forwards > 0 && c->depth_ready, "the last forward did not render depth (gsplat_context_set_depth)");
   *depth = c->depth_map.as<float>();
+  return GSPLAT_OK;
+}
+
+int gsplat_context_depth_moment_map(gsplat_context *c, const float **q) {
+  GS_REQUIRE(c && q, "null argument");
+  *q = nullptr;
+  GS_REQUIRE(c->n_forwards > 0 && c->depth_ready && c->depth_moment_ready,
+             "the last forward did not render the second moment (gsplat_context_set_depth_mode)");
+  *q = c->depth2_map.as<float>();
   return GSPLAT_OK;
 }
 

@@ -63,6 +63,7 @@ static int check_forward_args(const gsplat_context *c, const gsplat_gaussians *g
 // back from the pool, at their old sizes
 static int reclaim_outputs(gsplat_context *c, hipStream_t st) {
   c->have_forward = c->lists_ready = c->rows_ready = c->order_ready = c->depth_ready = c->rows_depth = c->rows_abs = false;
+  c->depth_inverse_ready = c->depth_moment_ready = false;
   gs::pool_unwatch(&c->last_mask);
   c->last_mask = nullptr;  // rank[] and compact_to_global are about to be overwritten
   gs::DeviceBuffer *outs[13];
@@ -88,6 +89,11 @@ static int plan_forward_call(gsplat_context *c, const gsplat_gaussians *g, const
   if (c->depth) {  // z from the compacted xyz_c, which preprocess writes in every mode
     if ((rc = c->depth_map.reserve((size_t)f.W * f.H * sizeof(float), st))) return rc;
     f.dmap.xyz_c = c->xyz_c.as<float>(); f.dmap.depth = c->depth_map.as<float>();
+    f.dmap.inverse = c->depth_inverse; f.dmap.moment = c->depth_moment;
+    if (c->depth_moment) {
+      if ((rc = c->depth2_map.reserve((size_t)f.W * f.H * sizeof(float), st))) return rc;
+      f.dmap.depth2 = c->depth2_map.as<float>();
+    }
   }
   f.compact = gs::compact_walk(c->N, c->M, f.N);
   if (f.compact && (rc = c->kept.reserve((size_t)c->max_gaussians * sizeof(int)))) return rc;
@@ -312,6 +318,7 @@ static int queue_sparse_tail(gsplat_context *c, FwdCall &f, size_t cap, long lon
     if ((r = c->seg_extra.reserve((want + 2) * sizeof(int2)))) return r;  // [want]: the count
     if ((r = c->seg_chk.reserve(slots * 256 * sizeof(float4)))) return r;
     if (c->depth && (r = c->seg_chk_d.reserve(slots * 256 * sizeof(float)))) return r;
+    if (c->depth && c->depth_moment && (r = c->seg_chk_q.reserve(slots * 256 * sizeof(float)))) return r;
     seg = backward_segments(c, (int)want);
     seg.asked = d_slot + 2;
     seg.tag = my_tag;
@@ -331,6 +338,7 @@ static int queue_sparse_tail(gsplat_context *c, FwdCall &f, size_t cap, long lon
     if ((r = c->fseg_gran.reserve(2 * want * 256 * sizeof(unsigned long long)))) return r;  // t products | final Ts
     if ((r = c->fseg_part.reserve(want * 256 * sizeof(float4)))) return r;
     if (c->depth && (r = c->fseg_part_d.reserve(want * 256 * sizeof(float)))) return r;
+    if (c->depth && c->depth_moment && (r = c->fseg_part_q.reserve(want * 256 * sizeof(float)))) return r;
     if ((r = c->fseg_stop.reserve(want * 256 * sizeof(int)))) return r;
     if (c->fseg_gran.ptr != c->fseg_gran_zeroed || c->fseg_gran.bytes != c->fseg_gran_zeroed_bytes) {
       GS_HIP(hipMemsetAsync(c->fseg_gran.ptr, 0, c->fseg_gran.bytes, st));  // tags of no epoch
@@ -360,6 +368,10 @@ static int queue_sparse_tail(gsplat_context *c, FwdCall &f, size_t cap, long lon
   if (c->depth) {
     a.depth.chk = split ? c->seg_chk_d.as<float>() : nullptr;
     a.depth.part = fsplit ? c->fseg_part_d.as<float>() : nullptr;
+    if (c->depth_moment) {
+      a.depth.chk2 = split ? c->seg_chk_q.as<float>() : nullptr;
+      a.depth.part2 = fsplit ? c->fseg_part_q.as<float>() : nullptr;
+    }
   }
   // Compact lists for the backward (gs_render.h: CompactLists): the one-workgroup-per-tile forward of a training context
   // writes them; a context that has seen a list beyond kSegSplitMin keeps the segment paths as they are.
@@ -451,6 +463,8 @@ static void record_forward(gsplat_context *c, const FwdCall &f, const gs::Forwar
   c->have_forward = !f.ro;  // a render-only forward leaves nothing for a backward
   c->lists_ready = true;
   c->depth_ready = c->depth;
+  c->depth_inverse_ready = c->depth && f.dmap.inverse;
+  c->depth_moment_ready = c->depth && f.dmap.moment;
   if (!out) return;
   const bool mid = f.mid;
   out->num_culled = (size_t)rec.M; out->num_pairs = (size_t)rec.pairs; out->num_splats = rec.S;
@@ -531,12 +545,18 @@ int gsplat_backward_render(gsplat_context *c, const float *grad_image, float bg_
 
 int gsplat_backward_render_split(gsplat_context *c, const float *grad_image, float bg_color, float *rgb_global,
                                  float *common, float *uv_norm, void *stream) {
-  return gsplat_backward_render_depth(c, grad_image, nullptr, nullptr, bg_color, rgb_global, common, uv_norm, stream);
+  return gsplat_backward_render_depth2(c, grad_image, nullptr, nullptr, nullptr, bg_color, rgb_global, common, uv_norm, stream);
 }
 
 int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, const float *grad_depth,
                                  const float *grad_alpha, float bg_color, float *rgb_global, float *common, float *uv_norm,
                                  void *stream) {
+  return gsplat_backward_render_depth2(c, grad_image, grad_depth, grad_alpha, nullptr, bg_color, rgb_global, common, uv_norm, stream);
+}
+
+int gsplat_backward_render_depth2(gsplat_context *c, const float *grad_image, const float *grad_depth,
+                                  const float *grad_alpha, const float *grad_depth2, float bg_color, float *rgb_global,
+                                  float *common, float *uv_norm, void *stream) {
   // (every check before the first launch: a refused call leaves the context and the caller's arrays as they were)
   GS_REQUIRE(c != nullptr, "null context");
   GS_REQUIRE(c->have_forward, "no forward pass recorded in this context");
@@ -548,10 +568,16 @@ int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, con
     GS_REQUIRE(((uintptr_t)common & 15) == 0, "common must be 16-byte aligned");
   }
   if (uv_norm) { GS_REQUIRE(common != nullptr, "uv_norm goes with common"); GS_REQUIRE_DEV(uv_norm); }
-  const bool depth = grad_depth != nullptr || grad_alpha != nullptr;  // both NULL: the plain backward, exactly
+  const bool depth = grad_depth != nullptr || grad_alpha != nullptr || grad_depth2 != nullptr;  // all NULL: the plain backward, exactly
   if (grad_depth) GS_REQUIRE_DEV(grad_depth);
   if (grad_alpha) GS_REQUIRE_DEV(grad_alpha);
+  if (grad_depth2) GS_REQUIRE_DEV(grad_depth2);
   GS_REQUIRE(!depth || c->depth_ready, "depth / alpha gradients need a forward that rendered depth (gsplat_context_set_depth)");
+  GS_REQUIRE(!grad_depth2 || c->depth_moment_ready,
+             "grad_depth2 needs a forward that rendered the second moment (gsplat_context_set_depth_mode)");
+  // (a forward with the moment option runs the moment backward whichever maps are given: a null dL/dQ reads as zero)
+  GS_REQUIRE(!(depth && c->depth_moment_ready && c->absgrad),
+             "the moment option has no absgrad form: depth gradients of such a forward cannot be taken in absgrad mode");
   hipStream_t st = (hipStream_t)stream;
   const int M = c->M, W = c->width, H = c->height;
   c->rows_ready = false;
@@ -588,6 +614,13 @@ int gsplat_backward_render_depth(gsplat_context *c, const float *grad_image, con
     if (c->seg_ready) a.depth.chk = c->seg_chk_d.as<float>();
     a.depth.grad_depth = grad_depth;
     a.depth.grad_alpha = grad_alpha;
+    a.depth.inverse = c->depth_inverse_ready;
+    if (c->depth_moment_ready) {
+      a.depth.moment = true;
+      a.depth.depth2 = c->depth2_map.as<float>();
+      if (c->seg_ready) a.depth.chk2 = c->seg_chk_q.as<float>();
+      a.depth.grad_depth2 = grad_depth2;
+    }
   }
   a.absgrad = c->absgrad;
   const int rc = gs::launch_render_bwd(a, st);
@@ -798,7 +831,7 @@ int gsplat_backward_gaussians_camera(gsplat_context *c, const gsplat_gaussians *
 static int backward_pass(const char *fn, gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
                          const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
                          int l_max, const gsplat_gradients *out, bool camera, float *grad_view, float *grad_campos,
-                         void *stream) {
+                         void *stream, const float *grad_depth2 = nullptr) {
   GS_REQUIRE_IN(fn, c && g && cam && (out || camera), "null argument struct");
   int rc = check_recorded_forward(fn, c, g, cam, l_max);
   if (rc) return rc;
@@ -808,8 +841,8 @@ static int backward_pass(const char *fn, gsplat_context *c, const gsplat_gaussia
   }
   if (out && (rc = check_gradient_arrays(fn, out, l_max))) return rc;
   // (the compositing half checks its own arguments before its first launch)
-  rc = gsplat_backward_render_depth(c, grad_image, grad_depth, grad_alpha, bg_color, /*rgb_global=*/nullptr,
-                                    /*common=*/nullptr, /*uv_norm=*/nullptr, stream);
+  rc = gsplat_backward_render_depth2(c, grad_image, grad_depth, grad_alpha, grad_depth2, bg_color, /*rgb_global=*/nullptr,
+                                     /*common=*/nullptr, /*uv_norm=*/nullptr, stream);
   if (rc) return rc;
   return backward_gaussians_impl(fn, c, g, cam, l_max, out, nullptr, nullptr, 0, g->num_gaussians, stream, nullptr, 2,
                                  nullptr, grad_view, grad_campos);
@@ -824,6 +857,13 @@ int gsplat_backward_pass_depth(gsplat_context *c, const gsplat_gaussians *g, con
                                const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
                                int l_max, const gsplat_gradients *out, void *stream) {
   return backward_pass(__func__, c, g, cam, grad_image, grad_depth, grad_alpha, bg_color, l_max, out, false, nullptr, nullptr, stream);
+}
+
+int gsplat_backward_pass_depth2(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,
+                                const float *grad_image, const float *grad_depth, const float *grad_alpha,
+                                const float *grad_depth2, float bg_color, int l_max, const gsplat_gradients *out, void *stream) {
+  return backward_pass(__func__, c, g, cam, grad_image, grad_depth, grad_alpha, bg_color, l_max, out, false, nullptr, nullptr, stream,
+                       grad_depth2);
 }
 
 int gsplat_backward_pass_camera(gsplat_context *c, const gsplat_gaussians *g, const gsplat_camera *cam,

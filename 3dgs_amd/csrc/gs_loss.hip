@@ -17,6 +17,8 @@
 // so the halo rows and columns shared by neighbouring tiles hit that XCD's L2 instead of being fetched 2.1 times
 // over the fabric (FETCH_SIZE 251 MB -> see profiles/).  The loss is reduced per wave on DPP and added to one of
 // 256 spread counters (a single hot atomic would serialise the adds), summed by the host when it asks for the value.
+#include <algorithm>
+
 #include "gs_common.h"
 #include "gs_render.h"
 #include "gs_math.h"
@@ -303,6 +305,70 @@ __global__ __launch_bounds__(256) void mse_kernel(long long n, const float *__re
   if ((threadIdx.x & 63) == 0) atomicAdd(&acc[(blockIdx.x * 4 + (threadIdx.x >> 6)) & (kSpread - 1)], s);
 }
 
+// ---- the depth regularisers (gsplat_distortion_loss, gsplat_depth_prior_loss): plain grid-stride kernels over the [H,W]
+// maps.  Per pixel everything is evaluated in double from the float maps and rounded to float once; the loss is summed in
+// double, per block into `partial` (null: no value asked for) and by reg_loss_finish_kernel in a fixed order.
+constexpr int kRegBlocks = 256;
+
+__device__ __forceinline__ void block_partial(double v, double *__restrict__ partial) {
+  __shared__ double s_wave[4];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
+}
+
+template <bool kAdd>
+__device__ __forceinline__ void put_grad(float *__restrict__ g, long long i, double v) {
+  if (!g) return;
+  if constexpr (kAdd) g[i] += (float)v;
+  else g[i] = (float)v;
+}
+
+// A = 1 - T, loss(p) = A Q - D^2, partials (Q, -2 D, A); `scale` = weight / P
+template <bool kAdd>
+__global__ __launch_bounds__(256) void distortion_loss_kernel(long long n, const float *__restrict__ T,
+                                                              const float *__restrict__ D, const float *__restrict__ Q,
+                                                              double scale, float *__restrict__ grad_alpha,
+                                                              float *__restrict__ grad_depth, float *__restrict__ grad_depth2,
+                                                              double *__restrict__ partial) {
+  double sum = 0.0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const double A = 1.0 - (double)T[i], d = (double)D[i], q = (double)Q[i];
+    sum += A * q - d * d;
+    put_grad<kAdd>(grad_alpha, i, scale * q);
+    put_grad<kAdd>(grad_depth, i, scale * (-2.0 * d));
+    put_grad<kAdd>(grad_depth2, i, scale * A);
+  }
+  if (partial) block_partial(sum, partial);
+}
+
+// |depth - target| over the pixels with target > 0; gradient scale x sign(depth - target), sign(0) = 0
+template <bool kAdd>
+__global__ __launch_bounds__(256) void depth_prior_loss_kernel(long long n, const float *__restrict__ depth,
+                                                               const float *__restrict__ target, double scale,
+                                                               float *__restrict__ grad_depth, double *__restrict__ partial) {
+  double sum = 0.0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float tg = target[i];
+    const double diff = tg > 0.0f ? (double)depth[i] - (double)tg : 0.0;
+    sum += fabs(diff);
+    put_grad<kAdd>(grad_depth, i, diff > 0.0 ? scale : diff < 0.0 ? -scale : 0.0);
+  }
+  if (partial) block_partial(sum, partial);
+}
+
+// one wave: the blocks' partial sums in a fixed order, x scale, as the one float of the loss
+__global__ __launch_bounds__(64) void reg_loss_finish_kernel(const double *__restrict__ partial, int n, double scale,
+                                                             float *__restrict__ loss_out) {
+  double v = 0.0;
+  for (int i = threadIdx.x; i < n; i += 64) v += partial[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if (threadIdx.x == 0) *loss_out = (float)(scale * v);
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(long long n, float *__restrict__ param,
                                                    const float *__restrict__ grad, float *__restrict__ m,
                                                    float *__restrict__ v, float lr, float b1, float b2, float eps,
@@ -577,6 +643,68 @@ int gsplat_fused_loss(const float *predicted_data, const float *gt_data, int row
     double total;
     if ((rc = read_spread_sum(cur, st, &total))) return rc;
     *loss_out = (float)(total / (double)((size_t)rows * cols * 3));
+  }
+  return GSPLAT_OK;
+}
+
+// what the two regularisers share behind their kernel: the blocks' partial sums -> loss_out
+static int reg_blocks(long long n) { return (int)std::min<long long>(kRegBlocks, (n + 255) / 256); }
+
+int gsplat_distortion_loss(const float *T, const float *depth, const float *depth2, int rows, int cols, float weight,
+                           int accumulate, float *grad_alpha, float *grad_depth, float *grad_depth2, float *loss_out,
+                           void *stream) {
+  GS_REQUIRE_DEV(T); GS_REQUIRE_DEV(depth); GS_REQUIRE_DEV(depth2);
+  if (grad_alpha) GS_REQUIRE_DEV(grad_alpha);
+  if (grad_depth) GS_REQUIRE_DEV(grad_depth);
+  if (grad_depth2) GS_REQUIRE_DEV(grad_depth2);
+  if (loss_out) GS_REQUIRE_DEV(loss_out);
+  GS_REQUIRE(rows > 0 && cols > 0, "image size must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  const long long n = (long long)rows * cols;
+  const double scale = (double)weight / (double)n;
+  const int blocks = reg_blocks(n);
+  gs::ScratchLock lock;
+  double *partial = nullptr;
+  if (loss_out) {
+    gs::DeviceBuffer &acc = gs::scratch(gs::SCR_DEPTH_LOSS);
+    if (int rc = acc.reserve(kRegBlocks * sizeof(double))) return rc;
+    partial = acc.as<double>();
+  }
+  if (accumulate)
+    distortion_loss_kernel<true><<<blocks, 256, 0, st>>>(n, T, depth, depth2, scale, grad_alpha, grad_depth, grad_depth2, partial);
+  else
+    distortion_loss_kernel<false><<<blocks, 256, 0, st>>>(n, T, depth, depth2, scale, grad_alpha, grad_depth, grad_depth2, partial);
+  GS_LAUNCH_CHECK();
+  if (loss_out) {
+    reg_loss_finish_kernel<<<1, 64, 0, st>>>(partial, blocks, scale, loss_out);
+    GS_LAUNCH_CHECK();
+  }
+  return GSPLAT_OK;
+}
+
+int gsplat_depth_prior_loss(const float *depth, const float *target, int rows, int cols, float weight, int accumulate,
+                            float *grad_depth, float *loss_out, void *stream) {
+  GS_REQUIRE_DEV(depth); GS_REQUIRE_DEV(target);
+  if (grad_depth) GS_REQUIRE_DEV(grad_depth);
+  if (loss_out) GS_REQUIRE_DEV(loss_out);
+  GS_REQUIRE(rows > 0 && cols > 0, "image size must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  const long long n = (long long)rows * cols;
+  const double scale = (double)weight / (double)n;
+  const int blocks = reg_blocks(n);
+  gs::ScratchLock lock;
+  double *partial = nullptr;
+  if (loss_out) {
+    gs::DeviceBuffer &acc = gs::scratch(gs::SCR_DEPTH_LOSS);
+    if (int rc = acc.reserve(kRegBlocks * sizeof(double))) return rc;
+    partial = acc.as<double>();
+  }
+  if (accumulate) depth_prior_loss_kernel<true><<<blocks, 256, 0, st>>>(n, depth, target, scale, grad_depth, partial);
+  else depth_prior_loss_kernel<false><<<blocks, 256, 0, st>>>(n, depth, target, scale, grad_depth, partial);
+  GS_LAUNCH_CHECK();
+  if (loss_out) {
+    reg_loss_finish_kernel<<<1, 64, 0, st>>>(partial, blocks, scale, loss_out);
+    GS_LAUNCH_CHECK();
   }
   return GSPLAT_OK;
 }

@@ -411,7 +411,9 @@ __device__ __forceinline__ RowsWeights make_rows_weights(int lane, float cx, flo
   return w;
 }
 
-// returns the register of the totals; `addr` <- off * 5 + acc_lane (the caller's atomic address, computed in the wait state)
+// returns the register of the totals; `addr` <- off * kMul + acc_lane (the caller's atomic address, computed in the wait
+// state; kMul = 5: ten doubles per slot, 6: the moment option's twelve, gs_render.h: DepthMaps)
+template <int kMul = 5>
 __device__ __forceinline__ float row_moments9r(float aT, float gp, const RowsWeights &w, unsigned int off, unsigned int acc_lane,
                                                unsigned int &addr) {
   float A, B, Q;
@@ -431,14 +433,14 @@ __device__ __forceinline__ float row_moments9r(float aT, float gp, const RowsWei
       "v_add_f32_dpp %[A], %[B], %[B] row_shr:4 row_mask:0xf bank_mask:0xa bound_ctrl:0\n\t"
       "v_add_f32_dpp %[Q], %[Q], %[Q] row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
       // (a VGPR written by VALU may be read through DPP two wait states later: Q's fold and the address cover A)
-      "v_mad_u32_u24 %[addr], %[off], 5, %[acc]\n\t"
+      "v_mad_u32_u24 %[addr], %[off], %[mul], %[acc]\n\t"
       // quads 8 lanes apart: banks 0,1 keep the A | B totals, banks 2,3 take Q's (bank 2: the total, bank 3: unused)
       "v_add_f32_dpp %[A], %[A], %[A] row_shl:8 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
       "v_add_f32_dpp %[A], %[Q], %[Q] row_shr:8 row_mask:0xf bank_mask:0xc bound_ctrl:0\n\t"
       : [A] "=&v"(A), [B] "=&v"(B), [Q] "=&v"(Q), [addr] "=&v"(addr)
       : [aT] "v"(aT), [gp] "v"(gp), [a0] "v"(w.a[0]), [a1] "v"(w.a[1]), [a2] "v"(w.a[2]), [a3] "v"(w.a[3]),
         [b0] "v"(w.b[0]), [b1] "v"(w.b[1]), [b2] "v"(w.b[2]), [b3] "v"(w.b[3]), [wq] "v"(w.q), [off] "v"(off),
-        [acc] "v"(acc_lane));
+        [acc] "v"(acc_lane), [mul] "n"(kMul));
   return A;
 }
 // which of the nine sums a lane holds after row_moments9r (0..2 rgb, 3 S_1, 4 S_cx, 5 S_cy, 6 S_cx2, 7 S_cxcy, 8 S_cy2; -1: none)
@@ -609,6 +611,26 @@ constexpr int kFwdPollBudget = 128, kFwdThinLayerDefault = 512;  // (gsplat_cont
 // slots of the colour ones: a segment's partial depth next to FwdSegments::part, the depth so far next to
 // TileSegments::chk.  The backward takes dL/d depth and dL/d alpha per pixel and adds sum aT * dL/d depth (= dL/d z) as
 // the tenth value of the gaussian's gradient row (slot 9), which preprocess_bwd_kernel adds to dL/d z_c.
+//
+// Two options of the mode (gsplat_context_set_depth_mode), each a template parameter of the kernels: the instantiations
+// with both off are the ones above, untouched.
+//  * inverse: the composited value is s = 1/z instead of z.  Staging writes s into the record's slot (r1.z forward, r1.w
+//    backward, the segment paths included) as ONE v_rcp_f32 (depth_value: 1 ulp, not an IEEE division -- both directions
+//    use the same instruction, so the backward sees the forward's s bit for bit; z > near_thresh > 0 for every compacted
+//    gaussian, so s is finite).  The chain rule ds/dz = -s^2 is applied where slot 9 is formed, in the backward's flush
+//    step 1: slot 9 stays dL/dz_c and preprocess_bwd_kernel is the depth mode's.
+//  * moment: the forward also composites Q(p) = sum_{i < n(p)} alpha_i T_i s_i^2 over background 0 (one multiply and one FMA
+//    next to the depth's), with side arrays next to the depth's (part2, chk2), and the backward takes a third map
+//    G_Q = dL/dQ: t gains s^2 G_Q (the depth's FMA becomes s (G_D + s G_Q), two), a segment entered at a boundary starts
+//    from (Q image - Q so far) / T_b as well, and dL/ds_i = sum_p aT G_D + 2 s_i sum_p aT G_Q needs one more row total.
+//    Route of that total: aT G_Q is no lane constant times aT once the colour register's four quad lanes are taken
+//    (rgb and G_D), so it is summed over the row on its own -- one product and the four DPP adds of row_sum -- and parked
+//    in lane 10 of the totals' register (Q's zero weight, as absgrad parks its first), where the trip's single
+//    ds_add_f64 adds it to accumulator 10; the accumulators are twelve doubles per slot as in absgrad mode
+//    (row_moments9r<6>).  The flush forms  res[9] = keep (acc[9] + 2 s acc[10]) (inverse ? -s^2 : 1)  in double.
+//    moment together with absgrad is REFUSED (GSPLAT_ERR_INVALID_ARG before anything is launched): absgrad parks its two
+//    totals in lanes 10 and 12 and fills accumulators 10 and 11, and a fourteen-double slot does not fit the kernel's LDS
+//    at seven workgroups per CU.
 struct DepthMaps {
   const float *xyz_c;       // [M,3] compacted camera-space positions (the context's c->xyz_c)
   float *depth;             // [H,W] the forward writes it; the backward reads it at segment boundaries
@@ -616,7 +638,20 @@ struct DepthMaps {
   float *chk;               // [TileSegments slots][256] the depth accumulated in front of a boundary
   const float *grad_depth;  // [H,W] backward: dL/d depth (null: zero)
   const float *grad_alpha;  // [H,W] backward: dL/d alpha (null: zero)
+  // the options (both off: everything below is unused)
+  float *depth2;             // [H,W] moment: Q, written and read like `depth`
+  float *part2;              // moment: a segment's partial Q, beside `part`
+  float *chk2;               // moment: Q so far, beside `chk`
+  const float *grad_depth2;  // [H,W] backward, moment: dL/dQ (null: zero)
+  bool inverse, moment;      // which instantiation the launchers pick
 };
+
+// what depth mode composites for a gaussian at camera-space depth z
+template <bool kInv>
+__device__ __forceinline__ float depth_value(float z) {
+  if constexpr (kInv) return __builtin_amdgcn_rcpf(z);
+  else return z;
+}
 
 // Compact lists for the backward (gsplat_context_set_compact_lists).  The tile lists come from the reference's box test,
 // and about a quarter of their entries (benchmark scene: 23.7 %) reach no 4x4 block of their tile with alpha >= 1/255:

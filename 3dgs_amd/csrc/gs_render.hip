@@ -259,7 +259,7 @@ __device__ __forceinline__ float fwd_t_product(const float4 *__restrict__ recs, 
 }
 
 // One segment of a long list (gs_render.h: FwdSegments).
-template <bool kPacked, bool kDepth>
+template <bool kPacked, bool kDepth, bool kInv = false, bool kMom = false>
 __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ recs, const RawSplats &raw,
                                                   const int *__restrict__ sorted, const int *__restrict__ ranges,
                                                   int width, int height, int ntx, unsigned short *__restrict__ masks_out,
@@ -303,6 +303,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
         if (k < m - 1) granule_store(gran_f, fs.epoch, 0.0f);
         *part = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if constexpr (kDepth) dm.part[(size_t)blk * 256 + tid] = 0.0f;
+        if constexpr (kMom) dm.part2[(size_t)blk * 256 + tid] = 0.0f;
         *stop = -2;
         return;
       }
@@ -327,6 +328,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
   const char *r2b = reinterpret_cast<const char *>(s_r2);
   const bool alive = inside && prefix >= kTMin;
   float tl = alive ? 1.0f : 0.0f, T = alive ? prefix : 0.0f, T_fin = -1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, ad = 0.0f;
+  [[maybe_unused]] float aq = 0.0f;  // (moment: Q, gs_render.h: DepthMaps)
   int n = -1;
   unsigned long long satmask = __ballot(!alive);
   int live = satmask != ~0ull ? 1 : 0;
@@ -343,7 +345,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
       stage_record(s);
       s.r1.w = __uint_as_float(hits);
       s.r2.w = s.r1.y > kLog2AlphaMax ? kLog2AlphaMax : s.r1.y;
-      if constexpr (kDepth) s.r1.z = dm.xyz_c[3 * g + 2];  // (gs_render.h: DepthMaps)
+      if constexpr (kDepth) s.r1.z = depth_value<kInv>(dm.xyz_c[3 * g + 2]);  // (gs_render.h: DepthMaps)
       s_r0[t] = s.r0; s_r1[t] = s.r1; s_r2[t] = s.r2;
     }
     __syncthreads();
@@ -381,6 +383,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
         ag = __builtin_fmaf(c0.y, w0, ag);
         ab = __builtin_fmaf(c0.z, w0, ab);
         if constexpr (kDepth) ad = __builtin_fmaf(z0, w0, ad);
+        if constexpr (kMom) aq = __builtin_fmaf(z0 * z0, w0, aq);
         const unsigned long long s0 = __ballot(tT0 < kTMin);
         tl = tl0;
         T = tT0;
@@ -396,6 +399,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
         ag = __builtin_fmaf(c1.y, w1, ag);
         ab = __builtin_fmaf(c1.z, w1, ab);
         if constexpr (kDepth) ad = __builtin_fmaf(z1, w1, ad);
+        if constexpr (kMom) aq = __builtin_fmaf(z1 * z1, w1, aq);
         const unsigned long long s1 = __ballot(tT1 < kTMin);
         tl = tl1;
         T = tT1;
@@ -415,6 +419,7 @@ __device__ __forceinline__ void fwd_segment_block(const float4 *__restrict__ rec
   if (k < m - 1) granule_store(gran_f, fs.epoch, T);
   *part = make_float4(ar, ag, ab, T_fin >= 0.0f ? T_fin : T);
   if constexpr (kDepth) dm.part[(size_t)blk * 256 + tid] = ad;
+  if constexpr (kMom) dm.part2[(size_t)blk * 256 + tid] = aq;
   *stop = T_fin >= 0.0f ? n : (alive ? -1 : -2);
 }
 
@@ -432,7 +437,7 @@ __device__ __forceinline__ int row_max_int(int v) {  // max over the 16 lanes of
 // kCompact: the forward also writes the compact lists for the backward (gs_render.h: CompactLists).  An instantiation of
 // its own, for the scalar registers: the kernel sits at the 8-waves budget of both register files, and the compact form
 // pays for its pointers and its running count with what the segment paths -- which it never runs beside -- hold.
-template <bool kPacked, bool kDepth = false, bool kCompact = false>
+template <bool kPacked, bool kDepth = false, bool kCompact = false, bool kInv = false, bool kMom = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVES, 8))) void render_fwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
                                                               const int *__restrict__ sorted,
                                                               const int *__restrict__ ranges, int width, int height,
@@ -445,6 +450,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
                                                               CompactLists cl) {
   static_assert(kPacked || !kDepth, "depth mode is a mode of the context's (packed) kernels");
   static_assert(kPacked || !kCompact, "compact lists are written by the context's (packed) forward");
+  static_assert(kDepth || (!kInv && !kMom), "inverse and moment are options of depth mode");
   __shared__ float4 s_r0[kBatch + 1], s_r1[kBatch + 1], s_r2[kBatch + 1];  // [kBatch]: the all-zero sentinel record
   __shared__ int s_tile_top;
   __shared__ int s_useful[4];  // compact lists (gs_render.h: CompactLists): the batch's useful slots, per staging wave
@@ -463,7 +469,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
   if constexpr (kPacked && !kCompact) {
     if (segmented && (int)blockIdx.x < fs.cap) {
       if ((int)blockIdx.x < *fs.count)
-        fwd_segment_block<kPacked, kDepth>(recs, raw, sorted, ranges, width, height, ntx, masks_out, fs, (int)blockIdx.x, s_r0, s_r1, s_r2, s_list, dm);
+        fwd_segment_block<kPacked, kDepth, kInv, kMom>(recs, raw, sorted, ranges, width, height, ntx, masks_out, fs, (int)blockIdx.x, s_r0, s_r1, s_r2, s_list, dm);
       return;
     }
   }
@@ -493,6 +499,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
   // A saturated pixel keeps T = 0 in the running transmittance, so every later splat blends with weight 0 and the
   // common path needs no per-pixel "done" masking; its real final transmittance and stop index live in T_fin / n.
   float T = inside ? 1.0f : 0.0f, T_fin = -1.0f, ar = 0.0f, ag = 0.0f, ab = 0.0f, ad = 0.0f;
+  [[maybe_unused]] float aq = 0.0f;  // (moment: Q, gs_render.h: DepthMaps)
   int n = total;
   unsigned long long satmask = __ballot(!inside);  // lanes whose pixel is saturated or outside the image
   int live = satmask != ~0ull ? 1 : 0;
@@ -513,6 +520,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
     if (checkpoints && base > 0 && base % kSegEntries == 0) {  // (gs_render.h: TileSegments)
       seg.chk[(size_t)segment_slot(start, base / kSegEntries) * 256 + t] = make_float4(T, ar, ag, ab);
       if constexpr (kDepth) dm.chk[(size_t)segment_slot(start, base / kSegEntries) * 256 + t] = ad;
+      if constexpr (kMom) dm.chk2[(size_t)segment_slot(start, base / kSegEntries) * 256 + t] = aq;
     }
 #if GS_STAMP
     ++st_batches;
@@ -540,7 +548,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
       // below 0.99f (the backward keeps its own 0.99f: it needs the uncapped value next to the capped one).  NaN stays NaN.
       s.r1.w = __uint_as_float(hits);
       s.r2.w = s.r1.y > kLog2AlphaMax ? kLog2AlphaMax : s.r1.y;
-      if constexpr (kDepth) s.r1.z = dm.xyz_c[3 * g + 2];  // (gs_render.h: DepthMaps; the loop never reads r1.z otherwise)
+      if constexpr (kDepth) s.r1.z = depth_value<kInv>(dm.xyz_c[3 * g + 2]);  // (gs_render.h: DepthMaps; the loop never reads r1.z otherwise)
       s_r0[t] = s.r0; s_r1[t] = s.r1; s_r2[t] = s.r2;
     }
     unsigned int rank = 0u;  // of a useful slot among its staging wave's useful slots, inclusive
@@ -612,6 +620,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
         ag = __builtin_fmaf(c0.y, w0, ag);
         ab = __builtin_fmaf(c0.z, w0, ab);
         if constexpr (kDepth) ad = __builtin_fmaf(z0, w0, ad);
+        if constexpr (kMom) aq = __builtin_fmaf(z0 * z0, w0, aq);
         const unsigned long long s0 = __ballot(tT0 < kTMin);  // this splat was still accumulated (render.cu:76-87)
         T = tT0;
         if (s0 != satmask) {  // rare: some pixel saturated with the trip's first splat
@@ -628,6 +637,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
         ag = __builtin_fmaf(c1.y, w1, ag);
         ab = __builtin_fmaf(c1.z, w1, ab);
         if constexpr (kDepth) ad = __builtin_fmaf(z1, w1, ad);
+        if constexpr (kMom) aq = __builtin_fmaf(z1 * z1, w1, aq);
         const unsigned long long s1 = __ballot(tT1 < kTMin);
         T = tT1;
         if (s1 != satmask) {  // rare: ... with its second
@@ -691,6 +701,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
     image[3 * pid + 1] = ag + Tout * bg;
     image[3 * pid + 2] = ab + Tout * bg;
     if constexpr (kDepth) dm.depth[pid] = ad;  // (background 0)
+    if constexpr (kMom) dm.depth2[pid] = aq;
     if (compact_all) cl.n_px[pid] = cbase;
   }
   if (compact && tid == 0) cl.count[tile] = cbase;
@@ -714,8 +725,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FWD_WAVE
 #ifndef GS_BWD_ABS_WAVES
 #define GS_BWD_ABS_WAVES 7
 #endif
-template <bool kPacked, bool kRows, int kB, bool kDepth = false, bool kAbs = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_BWD_ABS_WAVES : kDepth ? GS_BWD_DEPTH_WAVES : 8, 8))) void render_bwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
+// ... and the moment option's instantiations (gs_render.h: DepthMaps): twelve accumulators per slot as in absgrad mode
+#ifndef GS_BWD_MOMENT_WAVES
+#define GS_BWD_MOMENT_WAVES 7
+#endif
+template <bool kPacked, bool kRows, int kB, bool kDepth = false, bool kAbs = false, bool kInv = false, bool kMom = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_BWD_ABS_WAVES : kMom ? GS_BWD_MOMENT_WAVES : kDepth ? GS_BWD_DEPTH_WAVES : 8, 8))) void render_bwd_kernel(const float4 *__restrict__ recs, RawSplats raw,
                                                               const int *__restrict__ sorted,
                                                               const int *__restrict__ ranges,
                                                               const int *__restrict__ n_px,
@@ -727,12 +742,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
                                                               DepthMaps dm) {
   static_assert(kPacked || !kDepth, "depth mode is a mode of the context's (packed) kernels");
   static_assert(!kAbs || (kPacked && kRows), "absgrad mode is a mode of the context's kernel (row slots 10 and 11)");
+  static_assert(kDepth || (!kInv && !kMom), "inverse and moment are options of depth mode");
+  static_assert(!(kMom && kAbs), "the moment option and absgrad both park a total in lane 10 (gs_render.h: DepthMaps)");
   __shared__ float4 s_r0[kB + 1], s_r1[kB + 1];  // [kB]: the all-zero sentinel record
   // [slot][9]: rgb, S0, Sx, Sy, Sxx, Sxy, Syy.  Doubles on purpose: on gfx950 ds_add_f32 retires about one LANE
   // every three cycles while ds_add_f64 runs at LDS rate (profiles/microbench/lds_atomic_rate: 109 vs 16 cycles for
   // a 36-lane instruction), and the merge across the tile's 16 blocks needs one atomic per trip.
   // doubles per slot (nine used, ten in depth mode): 80 bytes = 5 x the list entry's byte offset; absgrad mode: twelve, 6 x
-  constexpr int kAcc = kAbs ? 12 : 10;
+  // (moment option: twelve as well, accumulator 10 = sum aT x dL/dQ)
+  constexpr int kAcc = kAbs || kMom ? 12 : 10;
   // gradient values per gaussian: row slots 0..8 (depth mode: and slot 9, dL/dz; absgrad mode: and 10, 11, sum |d/du|, |d/dv|)
   constexpr int kRes = kAbs ? 12 : kDepth ? 10 : 9;
   __shared__ double s_acc[(kB + 1) * kAcc];  // slot kB: the sentinel's (rows past the end of their list add zeros there)
@@ -789,6 +807,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
 
   int n = 0;
   float Tf = 0.0f, g0 = 0.0f, g1 = 0.0f, g2 = 0.0f, gD = 0.0f, gA = 0.0f;
+  [[maybe_unused]] float gQ = 0.0f;  // (moment option: dL/dQ)
   if (inside) {
     const int pid = py * width + px;
     n = n_px[pid];
@@ -797,6 +816,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
     if constexpr (kDepth) {
       if (dm.grad_depth) gD = dm.grad_depth[pid];
       if (dm.grad_alpha) gA = dm.grad_alpha[pid];
+    }
+    if constexpr (kMom) {
+      if (dm.grad_depth2) gQ = dm.grad_depth2[pid];
     }
   }
   // Running transmittance, and s = (pixel gradient) . (colour behind the current splat).  The colour behind only ever
@@ -817,7 +839,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
         // depth behind the boundary: (depth image - depth so far) / T_b; alpha behind it: (T_b - T_final) / T_b
         const float dk = dm.chk[(size_t)chk_slot * 256 + tid];
         s = (g0 * (seg.image[3 * pid] - ck.y) + g1 * (seg.image[3 * pid + 1] - ck.z) + g2 * (seg.image[3 * pid + 2] - ck.w) +
-             gD * (dm.depth[pid] - dk) + gA * (ck.x - Tf)) * inv;
+             gD * (dm.depth[pid] - dk) + gA * (ck.x - Tf));
+        if constexpr (kMom) s += gQ * (dm.depth2[pid] - dm.chk2[(size_t)chk_slot * 256 + tid]);  // Q behind the boundary, likewise
+        s *= inv;
       } else {
         s = (g0 * (seg.image[3 * pid] - ck.y) + g1 * (seg.image[3 * pid + 1] - ck.z) + g2 * (seg.image[3 * pid + 2] - ck.w)) * inv;
       }
@@ -851,7 +875,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
   // where this lane's share of the nine row totals goes (see row_moments9r), and the lane constants of the sums:
   // pixel position relative to the tile centre, pixel gradient
   // (depth mode: lane 3 of the row holds the tenth sum, aT x dL/d depth: the fourth channel of the colour register)
-  const int red_idx = kDepth && (lane & 15) == 3 ? 9 : kAbs ? row_moments9r_abs_index(lane) : row_moments9r_index(lane);
+  // (moment option: lane 10 of the row holds the eleventh, aT x dL/dQ, parked there behind the reduction)
+  const int red_idx = kDepth && (lane & 15) == 3 ? 9 : kMom && (lane & 15) == 10 ? 10 : kAbs ? row_moments9r_abs_index(lane) : row_moments9r_index(lane);
   const bool red_lane = red_idx >= 0;
   const float alpha_cap = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, __builtin_amdgcn_exp2f(kLog2AlphaMax))));
   const unsigned int acc_lane = (unsigned int)(size_t)(__attribute__((address_space(3))) char *)accb + (unsigned int)(red_idx * 8);
@@ -899,7 +924,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
         if (slot < count) {
           SplatRec s = pre;
           stage_record(s);
-          if constexpr (kDepth) s.r1.w = pre_z;  // (the loop never reads r1.w otherwise)
+          if constexpr (kDepth) s.r1.w = depth_value<kInv>(pre_z);  // (the loop never reads r1.w otherwise)
           s_r0[slot] = s.r0; s_r1[slot] = s.r1; s_r2[slot] = s.r2;
           s_id[slot] = pre_g;
         }
@@ -921,7 +946,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
         if constexpr (kPacked) s.r2.w = __uint_as_float((unsigned int)masks_in[start + base + t]);
         else s.r2.w = __uint_as_float(block_hits(s, tx0, ty0));
         stage_record(s);
-        if constexpr (kDepth) s.r1.w = dm.xyz_c[3 * g + 2];
+        if constexpr (kDepth) s.r1.w = depth_value<kInv>(dm.xyz_c[3 * g + 2]);
         s_r0[t] = s.r0; s_r1[t] = s.r1; s_r2[t] = s.r2;
         s_id[t] = g;
       }
@@ -1026,7 +1051,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
           const float aT = alpha * T;
           // t = grad . (colour - colour behind): three FMAs on the carried dot product
           float t = __builtin_fmaf(c.z, g2, __builtin_fmaf(c.y, g1, t0));
-          if constexpr (kDepth) t = __builtin_fmaf(b.w, gD, t);  // + z . dL/d depth (the alpha channel rides in s)
+          if constexpr (kMom) t = __builtin_fmaf(b.w, __builtin_fmaf(b.w, gQ, gD), t);  // + s . dL/dD + s^2 . dL/dQ
+          else if constexpr (kDepth) t = __builtin_fmaf(b.w, gD, t);  // + z . dL/d depth (the alpha channel rides in s)
           const float ga = t * T;                             // d/d alpha (cuda/render_backward.cu:139-151)
           s = __builtin_fmaf(alpha, t, s);                    // grad . colour behind the next (nearer) splat
           const float gp = og * ga;                           // d/d power
@@ -1036,7 +1062,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
           unsigned int acc_addr;
           float red;
           if constexpr (kAbs) red = row_moments9r_abs(aT, gp, pu, pv, rw, (unsigned int)off, acc_lane, acc_addr);
-          else red = row_moments9r(aT, gp, rw, (unsigned int)off, acc_lane, acc_addr);
+          else if constexpr (kMom) {
+            // the eleventh total on its own (gs_render.h: DepthMaps): one product, row_sum's four DPP adds, one select
+            const float rq = row_sum(aT * gQ);
+            red = row_moments9r<6>(aT, gp, rw, (unsigned int)off, acc_lane, acc_addr);
+            red = (lane & 15) == 10 ? rq : red;
+          } else red = row_moments9r(aT, gp, rw, (unsigned int)off, acc_lane, acc_addr);
           // Every lane that holds a sum adds it, zero or not (a compare to skip zeros costs more issue cycles than the
           // few extra lanes cost the LDS; rows past their list add zeros to the sentinel slot's accumulators).  32-bit
           // LDS address on purpose: through a generic pointer the compiler forms off * 5 with a 64-bit multiply-add.
@@ -1094,7 +1125,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbs ? GS_B
       res[6] = keep * (-0.5f * syy);                                                 // conic11
       res[7] = keep * (-(ca * sx + cb * sy) * (0.5f * (float)width));                // u (render_backward.cu:180-186)
       res[8] = keep * (-(cc * sy + cb * sx) * (0.5f * (float)height));               // v (:181-187)
-      if constexpr (kDepth) res[9] = keep * (float)acc[9];                            // dL/dz = sum aT dL/d depth
+      if constexpr (kInv || kMom) {
+        // b.w: the staged s.  dL/ds = sum aT dL/dD (+ 2 s sum aT dL/dQ), and ds/dz = -s^2 for s = 1/z: slot 9 stays dL/dz_c
+        const double sv = (double)b.w;
+        double ds = acc[9];
+        if constexpr (kMom) ds += 2.0 * sv * acc[10];
+        if constexpr (kInv) ds *= -(sv * sv);
+        res[9] = keep * (float)ds;
+      } else if constexpr (kDepth) res[9] = keep * (float)acc[9];                     // dL/dz = sum aT dL/d depth
       else if constexpr (kAbs) res[9] = 0.0f;
       if constexpr (kAbs) {
         // sum over the tile's pixels of |this pixel's share of d/du|, |.. d/dv|: ca dx + cb dy = kConicOff pu (stage_record)
@@ -1723,7 +1761,7 @@ __global__ __launch_bounds__(1024) void fwd_segments_table_kernel(const int *__r
 // ... and behind it: one block per tile adds up what the tile's segment blocks left (fixed order: the same image in every
 // run), finds the segment the pixel stopped in and writes the forward's per-pixel outputs, the tile's largest stop index
 // and the backward's checkpoints {T in front of the boundary, colour in front of it} (gs_render.h: TileSegments).
-template <bool kDepth = false>
+template <bool kDepth = false, bool kMom = false>
 __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__restrict__ ranges, int width, int height,
                                                                    int ntx, int num_tiles, float bg, int *__restrict__ n_out,
                                                                    float *__restrict__ T_out, float *__restrict__ image,
@@ -1743,6 +1781,7 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
   const int start = ranges[tile], total = ranges[tile + 1] - start;
   const int m = (total + kSegEntries - 1) / kSegEntries;
   float ar = 0.0f, ag = 0.0f, ab = 0.0f, ad = 0.0f, Tout = 1.0f;  // (depth: added in the colours' order)
+  [[maybe_unused]] float aq = 0.0f;                               // (moment: Q likewise)
   int n = total;
   // kAhead segments' values are requested before the first is looked at: one at a time the longest list's twenty
   // segments were twenty dependent round trips (28 us behind the forward)
@@ -1752,6 +1791,7 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
     int st[kAhead];
     float4 p[kAhead];
     float pref[kAhead], pd[kAhead];
+    [[maybe_unused]] float pq[kAhead];
 #pragma unroll
     for (int q = 0; q < kAhead; ++q) {
       const int k = min(k0 + q, m - 1);
@@ -1759,6 +1799,7 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
       st[q] = fs.stop[slot * 256 + tid];
       p[q] = fs.part[slot * 256 + tid];
       pd[q] = kDepth ? dm.part[slot * 256 + tid] : 0.0f;
+      if constexpr (kMom) pq[q] = dm.part2[slot * 256 + tid];
       // T in front of boundary k: what the segment in front left behind (read by the backward only for pixels that pass
       // the boundary alive, for which it is exactly the T segment k started from)
       pref[q] = k > 0 ? __uint_as_float((unsigned int)fs.granules[((size_t)fs.cap + fs.base[k - 1] + rank) * 256 + tid]) : 1.0f;
@@ -1770,10 +1811,12 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
       if (k > 0 && seg.chk) {
         seg.chk[(size_t)segment_slot(start, k) * 256 + tid] = make_float4(pref[q], ar, ag, ab);
         if constexpr (kDepth) dm.chk[(size_t)segment_slot(start, k) * 256 + tid] = ad;
+        if constexpr (kMom) dm.chk2[(size_t)segment_slot(start, k) * 256 + tid] = aq;
       }
       if (st[q] == -2) { done = true; break; }  // (a pixel outside the image; inside it a pixel is dead only behind the segment it stopped in)
       ar += p[q].x; ag += p[q].y; ab += p[q].z;
       if constexpr (kDepth) ad += pd[q];
+      if constexpr (kMom) aq += pq[q];
       Tout = p[q].w;
       if (st[q] >= 0) { n = st[q]; done = true; }
     }
@@ -1794,6 +1837,7 @@ __global__ __launch_bounds__(256) void fwd_segments_combine_kernel(const int *__
     image[3 * pid + 1] = ag + Tout * bg;
     image[3 * pid + 2] = ab + Tout * bg;
     if constexpr (kDepth) dm.depth[pid] = ad;
+    if constexpr (kMom) dm.depth2[pid] = aq;
   }
 }
 
@@ -1930,7 +1974,20 @@ int launch_render_fwd(const RenderFwdArgs &a, hipStream_t st) {
     launch_tiles(kernel, grid, st, nullptr, nullptr, a.recs, a.raw, a.sorted, a.ranges, a.width, a.height, ntx, num_tiles, a.bg,
                  a.n_out, a.T_out, a.image, a.zero, a.zero_vec, a.masks_out, nullptr, a.tops_out, seg, fs, a.depth, a.compact);
   };
-  if (compact) depth ? launch(render_fwd_kernel<true, true, true>) : launch(render_fwd_kernel<true, false, true>);
+  const bool inv = depth && a.depth.inverse, mom = depth && a.depth.moment;  // (gs_render.h: DepthMaps, the options)
+  GS_REQUIRE(!mom || a.depth.depth2, "the moment option needs its map");
+  if (inv || mom) {  // the options' own instantiations; the ones below are what they were
+    if (compact) {
+      if (inv && mom) launch(render_fwd_kernel<true, true, true, true, true>);
+      else if (mom) launch(render_fwd_kernel<true, true, true, false, true>);
+      else launch(render_fwd_kernel<true, true, true, true, false>);
+    } else {
+      if (inv && mom) launch(render_fwd_kernel<true, true, false, true, true>);
+      else if (mom) launch(render_fwd_kernel<true, true, false, false, true>);
+      else launch(render_fwd_kernel<true, true, false, true, false>);
+    }
+  }
+  else if (compact) depth ? launch(render_fwd_kernel<true, true, true>) : launch(render_fwd_kernel<true, false, true>);
   else if (packed) depth ? launch(render_fwd_kernel<true, true>) : launch(render_fwd_kernel<true>);
   else launch(render_fwd_kernel<false>);
   GS_LAUNCH_CHECK();
@@ -1938,7 +1995,8 @@ int launch_render_fwd(const RenderFwdArgs &a, hipStream_t st) {
     auto combine = [&](auto kernel) {
       kernel<<<num_tiles, 256, 0, st>>>(a.ranges, a.width, a.height, ntx, num_tiles, a.bg, a.n_out, a.T_out, a.image, a.tops_out, fs, seg, a.depth);
     };
-    depth ? combine(fwd_segments_combine_kernel<true>) : combine(fwd_segments_combine_kernel<false>);
+    if (mom) combine(fwd_segments_combine_kernel<true, true>);
+    else depth ? combine(fwd_segments_combine_kernel<true>) : combine(fwd_segments_combine_kernel<false>);
     GS_LAUNCH_CHECK();
   }
   return GSPLAT_OK;
@@ -1961,7 +2019,12 @@ int launch_render_bwd(const RenderBwdArgs &a, hipStream_t st) {
   constexpr int kB = GS_BWD_BATCH;
   // absgrad (gs_render.h: row_moments9r_abs) and depth mode (DepthMaps) are always the default loop: the ping-pong
   // experiment (render_bwd_pp_kernel: two half-batches in flight) has neither form
-  if (a.absgrad) depth ? launch(render_bwd_kernel<true, true, kB, true, true>) : launch(render_bwd_kernel<true, true, kB, false, true>);
+  const bool inv = depth && a.depth.inverse, mom = depth && a.depth.moment;  // (gs_render.h: DepthMaps, the options)
+  GS_REQUIRE(!(mom && a.absgrad), "the moment option has no absgrad form (gs_render.h: DepthMaps)");
+  GS_REQUIRE(!mom || a.depth.depth2, "the moment option needs its map");
+  if (mom) inv ? launch(render_bwd_kernel<true, true, kB, true, false, true, true>) : launch(render_bwd_kernel<true, true, kB, true, false, false, true>);
+  else if (inv) a.absgrad ? launch(render_bwd_kernel<true, true, kB, true, true, true>) : launch(render_bwd_kernel<true, true, kB, true, false, true>);
+  else if (a.absgrad) depth ? launch(render_bwd_kernel<true, true, kB, true, true>) : launch(render_bwd_kernel<true, true, kB, false, true>);
   else if (depth) launch(render_bwd_kernel<true, true, kB, true>);
   else if (packed && rows && pingpong)
     launch_tiles(render_bwd_pp_kernel, grid, st, a.ev_start, a.ev_stop, a.recs, a.sorted, a.ranges, a.n_px, a.T_px, a.grad_image,

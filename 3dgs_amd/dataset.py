@@ -201,7 +201,8 @@ def parseConfig(path):
 
 
 # keys this project adds to the flat `key: value` file; optional (ConfigParameters and its parser stay the reference's)
-EXTENSION_KEYS = dict(absgrad=False, antialiased=False, filter3d=False, prune_contribution=False, mcmc=False)
+EXTENSION_KEYS = dict(absgrad=False, antialiased=False, filter3d=False, prune_contribution=False, mcmc=False,
+                      distortion=False)
 
 
 def parseExtensions(path):

@@ -148,6 +148,48 @@ def fused_loss(predicted_data, gt_data, rows, cols, ssim_weight, image_grad, blo
     return float(out.value) if blocking else None
 
 
+def _map(t, name, shape=None):
+    """An [H,W] float32 device map for the depth regularisers; None stays None."""
+    if t is None:
+        return None
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+            or t.dim() != 2 or (shape is not None and tuple(t.shape) != tuple(shape))):
+        raise ValueError(f"{name} must be a contiguous [H,W] float32 device tensor" + (f" of shape {tuple(shape)}" if shape else ""))
+    return t
+
+
+def distortion_loss(fwd, weight, grad_alpha, grad_depth, grad_depth2, accumulate=False, blocking=False):
+    """The distortion loss of a forward that ran with the moment option (RasterContext.set_depth(True, moment=True)):
+    weight x mean over the pixels of A Q - D^2, A = 1 - fwd["T"], D = fwd["depth"], Q = fwd["depth2"], which is
+    sum_{j<i} w_i w_j (s_i - s_j)^2 of the pixel's splats (gsplat_distortion_loss; evaluated in double).  The three [H,W]
+    gradient maps (any may be None) get weight / P x (Q, -2 D, A) -- grad_alpha is dL/d(1 - T), what the backwards take --
+    overwritten, or added to with accumulate=True.  blocking=True returns the loss (a read-back), otherwise None."""
+    if "depth2" not in fwd:
+        raise ValueError("the forward did not render the second moment (RasterContext.set_depth(True, moment=True))")
+    T = _map(fwd["T"], "T")
+    H, W = T.shape
+    out = torch.empty(1, dtype=torch.float32, device=T.device) if blocking else None
+    check(_lib.load().gsplat_distortion_loss(
+        _p(T), _p(_map(fwd["depth"], "depth", (H, W))), _p(_map(fwd["depth2"], "depth2", (H, W))), int(H), int(W),
+        float(weight), int(bool(accumulate)), _p(_map(grad_alpha, "grad_alpha", (H, W))),
+        _p(_map(grad_depth, "grad_depth", (H, W))), _p(_map(grad_depth2, "grad_depth2", (H, W))), _p(out), _stream()))
+    return float(out.item()) if blocking else None
+
+
+def depth_prior_loss(depth, target, weight, grad_depth, accumulate=False, blocking=False):
+    """weight x mean over all H x W pixels of |depth - target| on the pixels with target > 0 (the others add nothing to
+    the loss or the gradient); grad_depth gets weight / P x sign(depth - target), overwritten or, with accumulate=True,
+    added to (gsplat_depth_prior_loss).  Whether the two maps hold z or 1/z is the caller's business.  blocking=True
+    returns the loss (a read-back), otherwise None."""
+    depth = _map(depth, "depth")
+    H, W = depth.shape
+    out = torch.empty(1, dtype=torch.float32, device=depth.device) if blocking else None
+    check(_lib.load().gsplat_depth_prior_loss(_p(depth), _p(_map(target, "target", (H, W))), int(H), int(W), float(weight),
+                                              int(bool(accumulate)), _p(_map(grad_depth, "grad_depth", (H, W))), _p(out),
+                                              _stream()))
+    return float(out.item()) if blocking else None
+
+
 def compute_psnr(predicted_data, gt_data, rows, cols):
     out = ctypes.c_float(0.0)
     check(_lib.load().gsplat_compute_psnr(_p(predicted_data), _p(gt_data), rows, cols, ctypes.byref(out), _stream()))

@@ -98,7 +98,7 @@ def _map_ptr(t):
     if t is None:
         return None
     if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
-        raise ValueError("grad_depth / grad_alpha must be contiguous [H,W] float32 device tensors")
+        raise ValueError("grad_depth / grad_alpha / grad_depth2 must be contiguous [H,W] float32 device tensors")
     return ctypes.c_void_p(t.data_ptr())
 
 
@@ -125,7 +125,7 @@ class RasterContext:
         check(self._lib.gsplat_context_create(ctypes.byref(h), int(max_gaussians), int(max_width), int(max_height)))
         self._h = h
         self._last = None
-        self._depth = False
+        self._depth = self._depth_inverse = self._depth_moment = False
         self._filter3d = self._filter3d_fwd = None
         self.max_gaussians, self.max_width, self.max_height = int(max_gaussians), int(max_width), int(max_height)
 
@@ -165,12 +165,19 @@ class RasterContext:
         recomputes what it needs); those four views are then absent from the forward's result."""
         check(self._lib.gsplat_context_set_lean_forward(self._h, int(bool(enabled))))
 
-    def set_depth(self, enabled):
+    def set_depth(self, enabled, inverse=False, moment=False):
         """Depth mode (gsplat_context_set_depth): every later forward also composites the per-pixel depth
         sum alpha T z (the result's "depth" view), and backward_pass / backward_render / backward_pass_adam accept
-        grad_depth / grad_alpha."""
-        check(self._lib.gsplat_context_set_depth(self._h, int(bool(enabled))))
+        grad_depth / grad_alpha.  Options (gsplat_context_set_depth_mode): inverse -- the composited value is s = 1/z
+        instead of z; moment -- the forward also composites sum alpha T s^2 (the result's "depth2" view) and the backwards
+        accept grad_depth2.  The moment option has no absgrad form."""
+        if enabled and (inverse or moment):
+            check(self._lib.gsplat_context_set_depth_mode(self._h, int(bool(inverse)), int(bool(moment))))
+        else:
+            check(self._lib.gsplat_context_set_depth(self._h, int(bool(enabled))))
         self._depth = bool(enabled)
+        self._depth_inverse = bool(enabled and inverse)
+        self._depth_moment = bool(enabled and moment)
 
     def set_absgrad(self, enabled):
         """Absgrad mode (gsplat_context_set_absgrad): from the next backward_render / backward_pass on, the compositing
@@ -317,6 +324,10 @@ class RasterContext:
             dp = ctypes.c_void_p()
             check(self._lib.gsplat_context_depth_map(self._h, ctypes.byref(dp)))
             out._specs["depth"] = (dp.value, (H, W), "<f4")
+            if self._depth_moment:
+                qp = ctypes.c_void_p()
+                check(self._lib.gsplat_context_depth_moment_map(self._h, ctypes.byref(qp)))
+                out._specs["depth2"] = (qp.value, (H, W), "<f4")
         out._derived["alpha"] = _alpha  # the opacity map: 1 - the final transmittance
         self._last = (g.num_gaussians, M, l_max)
         return out._all() if _EAGER_VIEWS else out
@@ -348,14 +359,20 @@ class RasterContext:
             setattr(gs, "grad_" + k, _ptr(grads.get(k)))
         return gs
 
-    def backward_pass(self, params, cam, grad_image, bg_color, l_max, grads, grad_depth=None, grad_alpha=None):
+    def backward_pass(self, params, cam, grad_image, bg_color, l_max, grads, grad_depth=None, grad_alpha=None,
+                      grad_depth2=None):
         """grads: dict from alloc_gradients (compacted order); every leaf gradient is overwritten.  grad_depth /
         grad_alpha ([H,W], depth mode, either may be None): dL/d of the forward's "depth" / "alpha" views, added to the
-        image's gradient (gsplat_backward_pass_depth)."""
+        image's gradient (gsplat_backward_pass_depth).  grad_depth2: dL/d of the "depth2" view (the moment option;
+        gsplat_backward_pass_depth2)."""
         g, c = self._structs(params, cam, l_max)
         gs = self._grad_struct(grads)
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if grad_depth is None and grad_alpha is None:
+        if grad_depth2 is not None:
+            check(self._lib.gsplat_backward_pass_depth2(self._h, ctypes.byref(g), ctypes.byref(c), _ptr(grad_image),
+                                                        _map_ptr(grad_depth), _map_ptr(grad_alpha), _map_ptr(grad_depth2),
+                                                        float(bg_color), int(l_max), ctypes.byref(gs), st))
+        elif grad_depth is None and grad_alpha is None:
             check(self._lib.gsplat_backward_pass(self._h, ctypes.byref(g), ctypes.byref(c), _ptr(grad_image),
                                                  float(bg_color), int(l_max), ctypes.byref(gs), st))
         else:
@@ -365,13 +382,13 @@ class RasterContext:
         return grads
 
     def backward_pass_adam(self, params, cam, grad_image, bg_color, l_max, adam, grads=None, grad_depth=None,
-                           grad_alpha=None):
+                           grad_alpha=None, grad_depth2=None):
         """backward_pass with the optimizer step inside (single-GPU training): the compositing backward, then ONE
         per-gaussian kernel that differentiates every visible gaussian and applies the masked Adam step to its rows of the
         parameters (`params`, in place), the moments and the densification statistics (gsplat_backward_gaussians_adam).
         adam: an _lib.AdamFused (AdamOptimizer.fused_state); grads: optional gradient arrays to fill as well;
-        grad_depth / grad_alpha: as in backward_pass."""
-        self.backward_render(grad_image, bg_color, grad_depth=grad_depth, grad_alpha=grad_alpha)
+        grad_depth / grad_alpha / grad_depth2: as in backward_pass."""
+        self.backward_render(grad_image, bg_color, grad_depth=grad_depth, grad_alpha=grad_alpha, grad_depth2=grad_depth2)
         self.backward_gaussians_adam(params, cam, l_max, adam, grads)
 
     def backward_gaussians_adam(self, params, cam, l_max, adam, grads=None):
@@ -383,14 +400,18 @@ class RasterContext:
                                                        ctypes.byref(adam), gs, st))
 
     def backward_render(self, grad_image, bg_color, rgb_global=None, common=None, uv_norm=None, grad_depth=None,
-                        grad_alpha=None):
+                        grad_alpha=None, grad_depth2=None):
         """First half of backward_pass: compositing backward; optionally this view's g_rgb in global order [N,3].
         common [N,12] (and uv_norm [N]): the split exchange's rows -- the rows of the gaussians this view culled are
         cleared here, the others are written by backward_gaussians_split (gsplat_backward_render_split).
-        grad_depth / grad_alpha: as in backward_pass; whichever per-gaussian call follows takes the depth term along
-        (gsplat_backward_render_depth)."""
+        grad_depth / grad_alpha / grad_depth2: as in backward_pass; whichever per-gaussian call follows takes the depth
+        term along (gsplat_backward_render_depth, gsplat_backward_render_depth2)."""
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if grad_depth is None and grad_alpha is None:
+        if grad_depth2 is not None:
+            check(self._lib.gsplat_backward_render_depth2(self._h, _ptr(grad_image), _map_ptr(grad_depth),
+                                                          _map_ptr(grad_alpha), _map_ptr(grad_depth2), float(bg_color),
+                                                          _ptr(rgb_global), _ptr(common), _ptr(uv_norm), st))
+        elif grad_depth is None and grad_alpha is None:
             check(self._lib.gsplat_backward_render_split(self._h, _ptr(grad_image), float(bg_color), _ptr(rgb_global),
                                                          _ptr(common), _ptr(uv_norm), st))
         else:

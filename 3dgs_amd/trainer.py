@@ -22,6 +22,8 @@ from .optimizer import AdamOptimizer, DEFAULT_LR
 
 GROUPS = ("xyz", "rgb", "sh", "opacity", "scale", "quaternion")
 
+DISTORTION_WEIGHT = 10.0  # the default of config key distortion_weight (README, "Depth regularisers")
+
 # config/base.yaml of the reference: the keys the loop reads
 DEFAULT_CONFIG = dict(
     DEFAULT_LR, near_thresh=0.3, mh_dist=3.0, cull_mask_padding=100, ssim_frac=0.2, use_background=True,
@@ -55,7 +57,19 @@ DEFAULT_CONFIG = dict(
     # mcmc_opacity_reg * mean sigmoid(opacity) + mcmc_scale_reg * mean exp(scale) to the rows the view saw.  One rank
     # only; the optimizer step runs behind the backward, as with antialiased
     mcmc=False, mcmc_min_opacity=0.005, mcmc_noise_lr=5e5, mcmc_grow_factor=1.05, mcmc_opacity_reg=0.01,
-    mcmc_scale_reg=0.01)
+    mcmc_scale_reg=0.01,
+    # distortion: from iteration distortion_start on (2DGS: 3000) every step adds distortion_weight x the mean over the
+    # pixels of sum_{j<i} w_i w_j (s_i - s_j)^2, the Mip-NeRF 360 distortion loss (ops.distortion_loss), with s = 1/z when
+    # distortion_inverse (the default: in raw z an unbounded capture's loss is its far content's) and s = z otherwise.
+    # distortion_weight: README, "Depth regularisers", has the numbers the default comes from.
+    # depth_prior: a view given as (camera, image, target) -- target an [H,W] float32 device tensor of inverse depth, <= 0
+    # where there is no data -- also adds w(it) x the mean of |depth - target| over the target's pixels
+    # (ops.depth_prior_loss), w decaying exponentially from depth_prior_weight_init to depth_prior_weight_final over
+    # num_iters like the position learning rate (Inria's depth regularisation); views without a target skip the term.
+    # With either key the context renders depth (RasterContext.set_depth, inverse as distortion_inverse, the second
+    # moment only with distortion).  One rank only; distortion has no absgrad form.
+    distortion=False, distortion_weight=DISTORTION_WEIGHT, distortion_start=3000, distortion_inverse=True,
+    depth_prior=False, depth_prior_weight_init=1.0, depth_prior_weight_final=0.01)
 
 
 def _logit(p):
@@ -90,7 +104,8 @@ def draw_view_indices(rng, iteration, world, num_views):
 
 class Trainer:
     """params: dict of device tensors (xyz rgb opacity scale quaternion, optionally sh) as gsplat_initialize_gaussians
-    returns them; views: list of (camera dict for raster.device_camera, ground-truth image tensor [H,W,3] on device)."""
+    returns them; views: list of (camera dict for raster.device_camera, ground-truth image tensor [H,W,3] on device) or,
+    for config key depth_prior, (camera, image, inverse-depth target [H,W] float32 on device)."""
 
     def __init__(self, params, views, config=None, scene_extent=1.0, seed=0, exchange="split", comm=None):
         """With an initialised torch.distributed group of W > 1 ranks the loop is view-sharded: every
@@ -124,6 +139,14 @@ class Trainer:
                 raise ValueError("mcmc trains on one rank: the sharded optimizer steps have no place for its regulariser")
             self.fused_adam = 0  # the regulariser is added to stored gradients, between the backward and the step
         self.mcmc_steps = []  # (iteration, gaussians relocated, gaussians added) of every MCMC refinement step
+        if self.cfg["distortion"] or self.cfg["depth_prior"]:
+            if self.world > 1:
+                raise ValueError("distortion / depth_prior train on one rank: the view-sharded step takes no depth gradients")
+            if self.cfg["distortion"] and self.cfg["absgrad"]:
+                raise ValueError("distortion has no absgrad form: the compositing backward refuses the second moment's "
+                                 "gradient in absgrad mode")
+        self._depth_maps = {}  # (H, W) -> the three gradient maps (dL/d alpha, dL/d depth, dL/d depth2), allocated once
+        self.last_regularisers = {}  # what the last train_step added: name -> weight
         self._filter3d = None       # [N] device tensor of the current gaussians; None: to be (re)computed
         self._filter3d_cams = None  # the training views' device camera arrays, built once
         self._sharded = None  # (key, ViewShardedStep) for the current gaussian count / SH degree
@@ -139,12 +162,9 @@ class Trainer:
         n = self.num_gaussians
         self.params["sh"] = params["sh"].contiguous() if self.l_max > 0 else \
             torch.zeros(n, 0, 3, dtype=torch.float32, device=self.params["xyz"].device)
-        W = max(int(c["width"]) for c, _ in views)
-        H = max(int(c["height"]) for c, _ in views)
-        self.ctx = raster.RasterContext(max(n, 1), W, H)
-        self.ctx.set_lean_forward(True)  # the loop only runs the fused backward, which recomputes Sigma / J / conic
-        self.ctx.set_absgrad(bool(self.cfg["absgrad"]))
-        self.ctx.set_antialiased(bool(self.cfg["antialiased"]))
+        W = max(int(v[0]["width"]) for v in views)
+        H = max(int(v[0]["height"]) for v in views)
+        self.ctx = self._new_context(max(n, 1), W, H)
         self.ctx_capacity = n
         self._new_optimizer(None)
         self.history = []
@@ -168,14 +188,19 @@ class Trainer:
             for g in self.opt.names:
                 self.opt.exp_avg[g], self.opt.exp_avg_sq[g] = moments[0][g], moments[1][g]
 
+    def _new_context(self, n, W, H):
+        ctx = raster.RasterContext(n, W, H)
+        ctx.set_lean_forward(True)  # the loop only runs the fused backward, which recomputes Sigma / J / conic
+        ctx.set_absgrad(bool(self.cfg["absgrad"]))
+        ctx.set_antialiased(bool(self.cfg["antialiased"]))
+        if self.cfg["distortion"] or self.cfg["depth_prior"]:  # (both off: the context is never put in depth mode)
+            ctx.set_depth(True, inverse=bool(self.cfg["distortion_inverse"]), moment=bool(self.cfg["distortion"]))
+        return ctx
+
     def _context_for(self, n):
         if n > self.ctx_capacity:  # the workspace is sized for a gaussian count: grow it geometrically
             self.ctx_capacity = int(n * 1.5) + 1
-            W, H = self.ctx.max_width, self.ctx.max_height
-            self.ctx = raster.RasterContext(self.ctx_capacity, W, H)
-            self.ctx.set_lean_forward(True)
-            self.ctx.set_absgrad(bool(self.cfg["absgrad"]))
-            self.ctx.set_antialiased(bool(self.cfg["antialiased"]))
+            self.ctx = self._new_context(self.ctx_capacity, self.ctx.max_width, self.ctx.max_height)
         self._set_filter3d(self.ctx)
         return self.ctx
 
@@ -187,7 +212,7 @@ class Trainer:
             return None
         if self._filter3d is None:
             if self._filter3d_cams is None:
-                self._filter3d_cams = ops.camera_arrays([c for c, _ in self.views], self.params["xyz"].device)
+                self._filter3d_cams = ops.camera_arrays([v[0] for v in self.views], self.params["xyz"].device)
             self._filter3d = ops.compute_filter3d(self.params["xyz"], *self._filter3d_cams,
                                                   near=float(self.cfg["filter3d_near"]))
         return self._filter3d
@@ -225,7 +250,43 @@ class Trainer:
             self._grads2 = (n, dict(xyz=torch.empty(n, 3, device=dev), precompute_rgb=torch.empty(n, 3, device=dev)))
         return {k: v[:m] for k, v in self._grads2[1].items()}
 
-    def train_step(self, cam, gt_image, want_loss=True):
+    def depth_prior_weight(self, it):
+        """The depth prior's weight at iteration `it`: exponential from depth_prior_weight_init to depth_prior_weight_final
+        over num_iters."""
+        c = self.cfg
+        w0, w1 = float(c["depth_prior_weight_init"]), float(c["depth_prior_weight_final"])
+        return w0 * (w1 / w0) ** (float(it) / float(c["num_iters"]))
+
+    def _depth_regularisers(self, fwd, it, H, W, depth_target):
+        """The depth terms of this iteration (config keys distortion, depth_prior), evaluated into the three reusable
+        [H,W] maps: dict(grad_alpha=, grad_depth=, grad_depth2=) for the backward -- empty when no term is active, and
+        then nothing here launches anything."""
+        c = self.cfg
+        self.last_regularisers = {}
+        distortion = bool(c["distortion"]) and it >= int(c["distortion_start"])
+        prior = bool(c["depth_prior"]) and depth_target is not None
+        if not (distortion or prior):
+            return {}
+        maps = self._depth_maps.get((H, W))
+        if maps is None:
+            dev = fwd["T"].device
+            maps = self._depth_maps[(H, W)] = tuple(torch.empty(H, W, dtype=torch.float32, device=dev) for _ in range(3))
+        g_alpha, g_depth, g_depth2 = maps
+        out = {}
+        if distortion:
+            w = float(c["distortion_weight"])
+            ops.distortion_loss(fwd, w, g_alpha, g_depth, g_depth2)
+            out = dict(grad_alpha=g_alpha, grad_depth=g_depth, grad_depth2=g_depth2)
+            self.last_regularisers["distortion"] = w
+        if prior:
+            w = self.depth_prior_weight(it)
+            ops.depth_prior_loss(fwd["depth"], depth_target, w, g_depth, accumulate=distortion)
+            out["grad_depth"] = g_depth
+            self.last_regularisers["depth_prior"] = w
+        return out
+
+    def train_step(self, cam, gt_image, want_loss=True, depth_target=None):
+        """depth_target: this view's inverse-depth prior (config key depth_prior), or None."""
         if self.world > 1:
             return self._train_step_sharded(cam, gt_image, want_loss)
         c = self.cfg
@@ -248,21 +309,24 @@ class Trainer:
         grad_image = self._grad_image_for(H, W, gt_image.device)
         # the loss value is a blocking read-back: only fetched when the caller logs it
         loss = ops.fused_loss(fwd["image"], gt_image, H, W, float(c["ssim_frac"]), grad_image, blocking=want_loss)
+        # the depth terms (config keys distortion, depth_prior; {} when none is active: the plain backward, exactly) ride
+        # with whichever backward the iteration runs -- the Adam-inside forms take the depth row as it is
+        dmaps = self._depth_regularisers(fwd, it, H, W, depth_target) if (c["distortion"] or c["depth_prior"]) else {}
         fused_adam = 0 if c["antialiased"] or c["filter3d"] or c["mcmc"] else self.fused_adam
         if fused_adam == 3:
             # r06: the SH group's step in a kernel that reads the coefficient rows once (update + the sums the position
             # gradient needs), then the per-gaussian backward with the five small groups' steps inside: no gradient arrays
-            ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it, mode=2))
+            ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it, mode=2), **dmaps)
         elif fused_adam == 2:
             # r06: the per-gaussian backward applies the optimizer step itself (no gradient arrays at all)
-            ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it))
+            ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it), **dmaps)
         elif fused_adam == 1:
             g2 = self._partial_gradients_for(ctx, fwd["num_culled"])
-            ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it, mode=1), g2)
+            ctx.backward_pass_adam(p, cam, grad_image, bg, self.l_max, self.opt.fused_state(it, mode=1), g2, **dmaps)
             self.opt.step_after_partial_backward(it, fwd, g2, cam["campos"])
         else:
             grads = self._gradients_for(ctx, fwd["num_culled"])
-            ctx.backward_pass(p, cam, grad_image, bg, self.l_max, grads)
+            ctx.backward_pass(p, cam, grad_image, bg, self.l_max, grads, **dmaps)
             if c["absgrad"]:  # the optimizer kernel takes the norm of what it is given as grad_uv: the absolute sums
                 grads = dict(grads, uv=ctx.absgrad_uv())
             if c["mcmc"]:
@@ -345,9 +409,11 @@ class Trainer:
         iterations, cuda/trainer.cu:1388), reported through on_eval(iteration, psnr)."""
         for _ in range(num_iters):
             v = self.draw_views()[self.rank]
-            cam, gt = self.views[v]
+            cam, gt = self.views[v][:2]
+            target = self.views[v][2] if len(self.views[v]) > 2 else None  # (config key depth_prior)
             want = bool(loss_every) and (self.iter % loss_every == 0 or (log_every and (self.iter + 1) % log_every == 0))
-            loss = self.train_step(cam, gt, want_loss=want)
+            loss = self.train_step(cam, gt, want_loss=want, depth_target=target) if target is not None else \
+                self.train_step(cam, gt, want_loss=want)
             if eval_every and (self.iter - 1) % eval_every == 0 and eval_views:
                 psnr = self.evaluate(eval_views)
                 if on_eval:
@@ -366,7 +432,7 @@ class Trainer:
         ctx = self._context_for(self.num_gaussians)
         ctx.set_render_only(True)  # nothing here runs a backward
         try:
-            for cam, gt in views:
+            for cam, gt in (v[:2] for v in views):
                 fwd = ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
                 total += ops.compute_psnr(fwd["image"], gt, int(cam["height"]), int(cam["width"]))
         finally:
@@ -388,7 +454,7 @@ class Trainer:
         ctx = self._context_for(n)
         ctx.set_render_only(True)
         try:
-            for cam, _ in (self.views if views is None else views):
+            for cam in (v[0] for v in (self.views if views is None else views)):
                 try:
                     ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
                 except Exception as e:  # no gaussian in view

@@ -531,6 +531,52 @@ int gsplat_backward_pass_depth(gsplat_context *ctx, const gsplat_gaussians *gaus
                                const float *grad_image, const float *grad_depth, const float *grad_alpha, float bg_color,
                                int l_max, const gsplat_gradients *out, void *stream);
 
+/* Inverse depth and the second moment (no ABI bump: new entry points only).  Two options of depth mode:
+ *   inverse   the composited value is s_i = 1/z_i instead of z_i (a v_rcp_f32, 1 ulp; z_i > near_thresh > 0):
+ *             depth(p) = sum alpha_i T_i / z_i, what a monocular inverse-depth prior is compared with;
+ *   moment    the forward also composites  depth2(p) = Q(p) = sum_{i < n(p)} alpha_i T_i s_i^2  over background 0.  With
+ *             A = 1 - weight_per_pixel, D = depth and Q, the distortion loss sum_{j<i} w_i w_j (s_i - s_j)^2 of a pixel is
+ *             A Q - D^2 (gsplat_distortion_loss).
+ *   gsplat_context_set_depth_mode     switches depth mode on with the options.  gsplat_context_set_depth(ctx, 1) is exactly
+ *                                     (0, 0); gsplat_context_set_depth(ctx, 0) clears everything;
+ *   gsplat_context_depth_moment_map   the [H,W] Q of the last forward, under gsplat_context_depth_map's rules; an error when
+ *                                     that forward ran without the moment option;
+ *   gsplat_backward_render_depth2     gsplat_backward_render_depth with grad_depth2 = dL/dQ ([H,W]) after grad_alpha; any of
+ *                                     the three maps may be NULL = zero.  dL/dz_i = (sum_p aT dL/dD + 2 s_i sum_p aT dL/dQ)
+ *                                     x (inverse ? -s_i^2 : 1) reaches grad_xyz through whichever per-gaussian call
+ *                                     follows (_range, _split, _camera and the Adam-inside forms included).  A non-NULL
+ *                                     grad_depth2 after a forward without the moment option: GSPLAT_ERR_INVALID_ARG
+ *                                     before anything is launched, the caller's arrays untouched.  The moment option has
+ *                                     no absgrad form: depth, alpha or moment gradients of a moment forward while
+ *                                     gsplat_context_set_absgrad is on are refused the same way;
+ *   gsplat_backward_pass_depth2       gsplat_backward_pass_depth with the same extra argument, under the same rules. */
+int gsplat_context_set_depth_mode(gsplat_context *ctx, int inverse, int moment);
+int gsplat_context_depth_moment_map(gsplat_context *ctx, const float **q);
+int gsplat_backward_render_depth2(gsplat_context *ctx, const float *grad_image, const float *grad_depth,
+                                  const float *grad_alpha, const float *grad_depth2, float bg_color, float *rgb_global,
+                                  float *common, float *uv_norm, void *stream);
+int gsplat_backward_pass_depth2(gsplat_context *ctx, const gsplat_gaussians *gaussians, const gsplat_camera *camera,
+                                const float *grad_image, const float *grad_depth, const float *grad_alpha,
+                                const float *grad_depth2, float bg_color, int l_max, const gsplat_gradients *out,
+                                void *stream);
+
+/* Depth regularisers on the maps above (plain grid-stride kernels; every map [rows, cols] float on the device).
+ *   gsplat_distortion_loss   A = 1 - T (T = weight_per_pixel).  Per pixel A Q - D^2 and its partials (Q, -2 D, A) are
+ *                            evaluated in double from the float maps (formed in float the difference cancels: 5e-5
+ *                            absolute on ordinary scenes).  loss = weight x mean over the P = rows x cols pixels;
+ *                            grad_alpha (= dL/d(1 - T), what the backward expects), grad_depth, grad_depth2 get
+ *                            weight / P x (Q, -2 D, A): overwritten, or added to when `accumulate` is set.  loss_out may be
+ *                            NULL; given, it is a device float, overwritten with the sum reduced in double.
+ *   gsplat_depth_prior_loss  weight x (1 / P) sum over the pixels with target > 0 of |depth - target|; the other pixels
+ *                            add nothing to the loss or the gradient.  grad_depth gets weight / P x sign(depth - target),
+ *                            sign(0) = 0 (overwritten, or added to with `accumulate`).  Whether depth and target are z or
+ *                            1/z is the caller's business. */
+int gsplat_distortion_loss(const float *T, const float *depth, const float *depth2, int rows, int cols, float weight,
+                           int accumulate, float *grad_alpha, float *grad_depth, float *grad_depth2, float *loss_out,
+                           void *stream);
+int gsplat_depth_prior_loss(const float *depth, const float *target, int rows, int cols, float weight, int accumulate,
+                            float *grad_depth, float *loss_out, void *stream);
+
 /* Camera gradient (no ABI bump: new entry points only).  view (camera->view[0..11] = [R|t]) and campos are two
  * independent inputs, as the forward reads them.  With c_j = dL/d xyz_c of visible gaussian j (projection, screen and
  * depth terms), p_j its world position, dM_j = dL/dM for M = J R and s_j its position gradient through the SH view

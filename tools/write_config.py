@@ -25,7 +25,7 @@ ORDER = ("dataset_path downsample_factor output_dir print_interval test_eval_int
          "max_sh_band add_sh_band_interval reset_opacity_interval reset_opacity_value reset_opacity_start reset_opacity_end "
          "use_split use_clone use_delete adaptive_control_start adaptive_control_end adaptive_control_interval max_gaussians "
          "delete_opacity_threshold uv_grad_threshold split_scale_factor").split()
-EXTENSIONS = ("absgrad", "antialiased", "filter3d", "prune_contribution", "mcmc")  # optional keys behind ConfigParameters' (3dgs_amd/dataset.py: EXTENSION_KEYS)
+EXTENSIONS = ("absgrad", "antialiased", "filter3d", "prune_contribution", "mcmc", "distortion")  # optional keys behind ConfigParameters' (3dgs_amd/dataset.py: EXTENSION_KEYS)
 
 
 def main():
