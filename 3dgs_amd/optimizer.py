@@ -13,10 +13,9 @@ import torch
 from . import _lib
 from .dist import packed_layout
 from .ops import check
+from .rows import GROUPS
 
 B1, B2, EPS = 0.9, 0.999, 1e-8  # include/gsplat_cuda/optimizer.cuh:9-11
-
-GROUPS = ("xyz", "rgb", "sh", "opacity", "scale", "quaternion")
 
 # config/base.yaml of the reference (learning-rate multipliers of ConfigParameters)
 DEFAULT_LR = dict(base_lr=1e-3, xyz_lr_multiplier_init=1.6e-1, xyz_lr_multiplier_final=1.6e-3, quat_lr_multiplier=1.0,
@@ -31,18 +30,24 @@ def _stream():
 class AdamOptimizer:
     """Adam state (exp_avg / exp_avg_sq per group, global order) + densification accumulators.
 
-    params: dict name -> device tensor [N, stride] (xyz rgb sh opacity scale quaternion); updated in place."""
+    params: dict name -> device tensor [N, stride] (xyz rgb sh opacity scale quaternion); updated in place.
+    state: (exp_avg, exp_avg_sq, uv_grad_accum, grad_accum_dur) to go on from, adopted as they are (the Trainer's row
+    edits: Trainer._install); default: all of it starts at zero."""
 
-    def __init__(self, params, l_max, lr_config=None, scene_extent=1.0):
+    def __init__(self, params, l_max, lr_config=None, scene_extent=1.0, state=None):
         self.params, self.l_max = params, l_max
         self.cfg = dict(DEFAULT_LR, **(lr_config or {}))
         self.scene_extent = float(scene_extent)
         self.names = [g for g in GROUPS if not (g == "sh" and l_max == 0)]
-        self.exp_avg = {g: torch.zeros_like(params[g]) for g in self.names}
-        self.exp_avg_sq = {g: torch.zeros_like(params[g]) for g in self.names}
-        n = params["xyz"].shape[0]
-        self.uv_grad_accum = torch.zeros(n, device=params["xyz"].device)       # OptimizerAccumulators
-        self.grad_accum_dur = torch.zeros(n, dtype=torch.int32, device=params["xyz"].device)
+        if state is not None:
+            exp_avg, exp_avg_sq, self.uv_grad_accum, self.grad_accum_dur = state
+            self.exp_avg, self.exp_avg_sq = ({g: m[g] for g in self.names} for m in (exp_avg, exp_avg_sq))
+        else:
+            self.exp_avg = {g: torch.zeros_like(params[g]) for g in self.names}
+            self.exp_avg_sq = {g: torch.zeros_like(params[g]) for g in self.names}
+            n = params["xyz"].shape[0]
+            self.uv_grad_accum = torch.zeros(n, device=params["xyz"].device)       # OptimizerAccumulators
+            self.grad_accum_dur = torch.zeros(n, dtype=torch.int32, device=params["xyz"].device)
         self.cols, self.width = packed_layout(l_max)
 
     def learning_rates(self, it):

@@ -19,8 +19,7 @@ import torch
 from . import ops, raster
 from .dist import TorchComm, ViewShardedStep
 from .optimizer import AdamOptimizer, DEFAULT_LR
-
-GROUPS = ("xyz", "rgb", "sh", "opacity", "scale", "quaternion")
+from .rows import MOMENT, PARAM, STAT, RowTable
 
 DISTORTION_WEIGHT = 10.0  # the default of config key distortion_weight (README, "Depth regularisers")
 
@@ -74,6 +73,12 @@ DEFAULT_CONFIG = dict(
 
 def _logit(p):
     return math.log(p) - math.log(1.0 - p)
+
+
+def _compact_rows(t, keep, keep_n):
+    """The keep_n rows of t ([N, ...] float32) whose byte of `keep` ([N] uint8) is set, in order."""
+    stride = t.numel() // t.shape[0]
+    return ops.compact_masked_array(stride, t.reshape(-1), keep, keep_n).reshape((keep_n,) + tuple(t.shape[1:]))
 
 
 def contribution_prune_mask(weight_max, pixels, threshold):
@@ -131,7 +136,7 @@ class Trainer:
         #     219 + 113 us, 10 us of the 1100, no gradient arrays at all;
         #   2: all six groups inside the backward (one fat kernel at three waves per SIMD: 356 us, 2 % slower);
         #   0: the backward stores its gradients, the two optimizer kernels read them (r01-r05).
-        self.fused_adam = int(__import__("os").environ.get("GSPLAT_FUSED_ADAM", "1") or 0)
+        self.fused_adam = int(os.environ.get("GSPLAT_FUSED_ADAM", "1") or 0)
         if self.cfg["antialiased"] or self.cfg["filter3d"]:
             self.fused_adam = 0  # whatever the environment says: the Adam-inside backward refuses the modes
         if self.cfg["mcmc"]:
@@ -152,6 +157,7 @@ class Trainer:
         self._sharded = None  # (key, ViewShardedStep) for the current gaussian count / SH degree
         self._grad_image = {}  # (H, W) -> dL/dimage buffer, allocated once per image size
         self._grads = None     # (capacity, l_max, dict): per-view gradient arrays, reused across iterations
+        self._grads2 = None    # (capacity, dict): the two arrays behind a partial backward_pass_adam, reused likewise
         self.scene_extent = float(scene_extent)
         self.seed = int(seed)
         self.rng = np.random.default_rng(seed)
@@ -166,7 +172,7 @@ class Trainer:
         H = max(int(v[0]["height"]) for v in views)
         self.ctx = self._new_context(max(n, 1), W, H)
         self.ctx_capacity = n
-        self._new_optimizer(None)
+        self._install(RowTable.fresh(self.params))
         self.history = []
         self.contribution_prunes = []  # (iteration, gaussians removed) of every scheduled prune_by_contribution
         self._set_filter3d(self.ctx)
@@ -176,17 +182,27 @@ class Trainer:
     def num_gaussians(self):
         return int(self.params["xyz"].shape[0])
 
-    def _new_optimizer(self, moments):
-        """Fresh AdamOptimizer over the current parameter tensors; `moments` = (exp_avg, exp_avg_sq) dicts to adopt."""
-        self._sharded = None  # the parameter tensors were replaced: the exchange step binds to the new ones
-        self._filter3d = None  # ... and the gaussian set or its order changed (density control, Morton re-order)
-        p = dict(self.params)
-        if self.l_max == 0:
-            p.pop("sh")
-        self.opt = AdamOptimizer(p, self.l_max, lr_config=self.cfg, scene_extent=self.scene_extent)
-        if moments is not None:
-            for g in self.opt.names:
-                self.opt.exp_avg[g], self.opt.exp_avg_sq[g] = moments[0][g], moments[1][g]
+    def _rows(self):
+        """Everything that has a row per gaussian, as it stands."""
+        o = self.opt
+        return RowTable(self.params, o.exp_avg, o.exp_avg_sq, o.uv_grad_accum, o.grad_accum_dur)
+
+    def _install(self, rows):
+        """Make `rows` (a RowTable) the run's state: the parameters, the SH degree their `sh` column has, and an
+        AdamOptimizer over those very tensors that goes on from the table's moments and statistics.  The one place a new
+        row set or row order comes in, so what depends on either is dropped here."""
+        rows.check()
+        sh = rows.params["sh"]
+        l_max = math.isqrt(sh.shape[1] + 1) - 1 if sh.dim() == 3 else -1
+        if tuple(sh.shape[1:]) != ((l_max + 1) ** 2 - 1, 3):
+            raise ValueError("sh is %s: not the coefficients of an SH degree" % (tuple(sh.shape),))
+        self.l_max = l_max
+        self.params = dict(rows.params)
+        self.opt = AdamOptimizer({g: self.params[g] for g in rows.exp_avg}, self.l_max, lr_config=self.cfg,
+                                 scene_extent=self.scene_extent,
+                                 state=(rows.exp_avg, rows.exp_avg_sq, rows.uv_grad_accum, rows.grad_accum_dur))
+        self._sharded = None   # the exchange step is bound to the tensors that were replaced
+        self._filter3d = None  # the gaussian set or its order changed
 
     def _new_context(self, n, W, H):
         ctx = raster.RasterContext(n, W, H)
@@ -245,7 +261,7 @@ class Trainer:
     def _partial_gradients_for(self, ctx, m):
         """The two arrays the optimizer kernels behind a partial backward_pass_adam read: grad_xyz, grad_precompute_rgb."""
         n = self.num_gaussians
-        if getattr(self, "_grads2", None) is None or self._grads2[0] < n:
+        if self._grads2 is None or self._grads2[0] < n:
             dev = self.params["xyz"].device
             self._grads2 = (n, dict(xyz=torch.empty(n, 3, device=dev), precompute_rgb=torch.empty(n, 3, device=dev)))
         return {k: v[:m] for k, v in self._grads2[1].items()}
@@ -285,18 +301,23 @@ class Trainer:
             self.last_regularisers["depth_prior"] = w
         return out
 
-    def train_step(self, cam, gt_image, want_loss=True, depth_target=None):
-        """depth_target: this view's inverse-depth prior (config key depth_prior), or None."""
-        if self.world > 1:
-            return self._train_step_sharded(cam, gt_image, want_loss)
-        c = self.cfg
-        it = self.iter
+    def _begin_step(self):
+        """What an iteration starts with on one rank and on many: -> (iteration, background, context).  The SH band is
+        added first: the context is sized and its 3D filter set for the gaussians the step trains."""
+        c, it = self.cfg, self.iter
         # cuda/trainer.cu:1341-1343: the background cycles for the whole run (use_background_end is parsed but never read)
         bg = (it % 255) / 255.0 if c["use_background"] else 0.0
         if it % c["add_sh_band_interval"] == 0 and it >= c["add_sh_band_interval"]:
             self.add_sh_band()
         self._refresh_filter3d(it)
-        ctx = self._context_for(self.num_gaussians)
+        return it, bg, self._context_for(self.num_gaussians)
+
+    def train_step(self, cam, gt_image, want_loss=True, depth_target=None):
+        """depth_target: this view's inverse-depth prior (config key depth_prior), or None."""
+        if self.world > 1:
+            return self._train_step_sharded(cam, gt_image, want_loss)
+        c = self.cfg
+        it, bg, ctx = self._begin_step()
         p = dict(self.params)
         H, W = int(cam["height"]), int(cam["width"])
         try:
@@ -312,7 +333,7 @@ class Trainer:
         # the depth terms (config keys distortion, depth_prior; {} when none is active: the plain backward, exactly) ride
         # with whichever backward the iteration runs -- the Adam-inside forms take the depth row as it is
         dmaps = self._depth_regularisers(fwd, it, H, W, depth_target) if (c["distortion"] or c["depth_prior"]) else {}
-        fused_adam = 0 if c["antialiased"] or c["filter3d"] or c["mcmc"] else self.fused_adam
+        fused_adam = self.fused_adam  # (0 with antialiased, filter3d or mcmc: decided in __init__)
         if fused_adam == 3:
             # r06: the SH group's step in a kernel that reads the coefficient rows once (update + the sums the position
             # gradient needs), then the per-gaussian backward with the five small groups' steps inside: no gradient arrays
@@ -344,16 +365,10 @@ class Trainer:
         """One iteration of a W-rank group: this rank's view -> loss -> backward -> exchange -> the same optimizer step on
         every rank, incl. the densification statistics (split exchange: AdamOptimizer.step_split on common + rgb_all;
         the other payloads: gsplat_optimizer_step_packed on the packed rows)."""
-        c, it = self.cfg, self.iter
-        bg = (it % 255) / 255.0 if c["use_background"] else 0.0
-        if it % c["add_sh_band_interval"] == 0 and it >= c["add_sh_band_interval"]:
-            self.add_sh_band()
-        self._refresh_filter3d(it)
-        n = self.num_gaussians
-        key = (n, self.l_max)
-        self._context_for(n)  # (the step below runs on this context, with the current 3D filter set)
+        c = self.cfg
+        it, bg, ctx = self._begin_step()  # (the step below runs on this context, with the current 3D filter set)
+        key = (self.num_gaussians, self.l_max)
         if self._sharded is None or self._sharded[0] != key:
-            ctx = self._context_for(n)
             p = dict(self.params)
             self._sharded = (key, ViewShardedStep(p, self.l_max, ctx.max_width, ctx.max_height, c, 0.0,
                                                   exchange=self.exchange, with_uv_norm=True, ctx=ctx, comm=self.comm,
@@ -486,19 +501,8 @@ class Trainer:
         if n_remove == 0:
             return 0
         keep, keep_n = (~remove).to(torch.uint8).contiguous(), n - n_remove
-
-        def compact(t):
-            if t.numel() == 0:  # no SH coefficients yet
-                return t[:keep_n].contiguous()
-            stride = t.numel() // n
-            return ops.compact_masked_array(stride, t.reshape(-1), keep, keep_n).reshape((keep_n,) + tuple(t.shape[1:]))
-
-        self.params = {g: compact(t) for g, t in self.params.items()}
-        m = ({g: compact(self.opt.exp_avg[g]) for g in self.opt.names},
-             {g: compact(self.opt.exp_avg_sq[g]) for g in self.opt.names})
-        acc = (compact(self.opt.uv_grad_accum), compact(self.opt.grad_accum_dur.view(torch.float32)).view(torch.int32))
-        self._new_optimizer(m)
-        self.opt.uv_grad_accum, self.opt.grad_accum_dur = acc
+        # parameters, moments and statistics alike: the survivors' rows move up
+        self._install(self._rows().map(lambda kind, name, t: _compact_rows(t, keep, keep_n)))
         return n_remove
 
     # ------------------------------------------------------------------ policy steps
@@ -514,17 +518,13 @@ class Trainer:
     def add_sh_band(self):  # cuda/trainer.cu:377-413
         if self.l_max >= self.cfg["max_sh_band"]:
             return
-        old = self.l_max
-        m = ({g: self.opt.exp_avg[g] for g in self.opt.names}, {g: self.opt.exp_avg_sq[g] for g in self.opt.names})
-        acc = (self.opt.uv_grad_accum, self.opt.grad_accum_dur)
-        self.params["sh"] = ops.expand_sh(self.params["sh"], old)
-        if old == 0:
-            m[0]["sh"], m[1]["sh"] = torch.zeros_like(self.params["sh"]), torch.zeros_like(self.params["sh"])
-        else:
-            m[0]["sh"], m[1]["sh"] = ops.expand_sh(m[0]["sh"], old), ops.expand_sh(m[1]["sh"], old)
-        self.l_max = old + 1
-        self._new_optimizer(m)
-        self.opt.uv_grad_accum, self.opt.grad_accum_dur = acc
+        # the same rows with a wider `sh` column, so not a map: `sh` and its two moments are re-laid out with the new band
+        # zero (the first band's moments start at zero: there were none); the other groups and the statistics are kept
+        old, rows = self.l_max, self._rows()
+        sh = ops.expand_sh(rows.params["sh"], old)
+        m, v = (ops.expand_sh(mom["sh"], old) if old else torch.zeros_like(sh) for mom in (rows.exp_avg, rows.exp_avg_sq))
+        self._install(RowTable(dict(rows.params, sh=sh), dict(rows.exp_avg, sh=m), dict(rows.exp_avg_sq, sh=v),
+                               rows.uv_grad_accum, rows.grad_accum_dur))
 
     def adaptive_density_step(self):  # cuda/trainer.cu:518-779
         c, n = self.cfg, self.num_gaussians
@@ -573,29 +573,15 @@ class Trainer:
                                 seed=self.seed * 1000003 + self.iter)
         keep_n = n - n_prune - n_split
 
-        def rebuild(t, stride, new_rows):
-            if stride == 0:  # no SH coefficients yet
-                return torch.empty(new_n, 0, device=dev)
-            kept = ops.compact_masked_array(stride, t.reshape(-1), keep, keep_n)
-            parts = [kept.reshape(keep_n, stride)] + [r.reshape(-1, stride) for r in new_rows]
-            return torch.cat(parts, 0)
+        def relayout(kind, g, t):  # -> [kept | clones | split pairs]
+            if kind == STAT:  # zero: maintenance() resets the statistics behind every density step anyway
+                return t.new_zeros(new_n)
+            kept, row = _compact_rows(t, keep, keep_n), tuple(t.shape[1:])
+            if kind == MOMENT:  # kept rows keep their moments, new rows start at zero (cuda/trainer.cu:703-742)
+                return torch.cat([kept, t.new_zeros((n_add,) + row)], 0)
+            return torch.cat([kept, clones[g].reshape((n_clone,) + row), splits[g].reshape((2 * n_split,) + row)], 0)
 
-        shape = dict(xyz=3, rgb=3, opacity=1, scale=3, quaternion=4, sh=nsh * 3)
-        new_params, m, v = {}, {}, {}
-        for g in GROUPS:
-            s = shape[g]
-            new_params[g] = rebuild(self.params[g], s, [clones[g], splits[g]])
-            if g in self.opt.names:  # kept rows keep their moments, new rows start at zero (cuda/trainer.cu:703-742)
-                z = [torch.zeros(n_clone, s, device=dev), torch.zeros(2 * n_split, s, device=dev)]
-                m[g] = rebuild(self.opt.exp_avg[g], s, z)
-                v[g] = rebuild(self.opt.exp_avg_sq[g], s, z)
-        self.params = dict(xyz=new_params["xyz"], rgb=new_params["rgb"], opacity=new_params["opacity"].reshape(-1),
-                           scale=new_params["scale"], quaternion=new_params["quaternion"],
-                           sh=new_params["sh"].reshape(new_n, nsh, 3))
-        for g in m:
-            tgt = self.params[g].shape
-            m[g], v[g] = m[g].reshape(tgt).contiguous(), v[g].reshape(tgt).contiguous()
-        self._new_optimizer((m, v))
+        self._install(self._rows().map(relayout))
         return dict(pruned=n_prune, cloned=n_clone, split=n_split, skipped=False)
 
     # ------------------------------------------------------------------ MCMC densification (config key mcmc)
@@ -619,13 +605,17 @@ class Trainer:
         samples, counts = ops.sample_by_weight(weights, k, self._mcmc_seed(self.iter - 1) if seed is None else seed)
         ops.mcmc_relocate(opacity, self.params["scale"], counts, float(c["mcmc_min_opacity"]))
         src = samples.long()
-        for t in self.params.values():  # after the update: the copies carry the new opacity and scale
-            if t.numel():
+        restart = torch.cat([src, dead_idx])
+
+        def relocate(kind, name, t):
+            if kind == PARAM:  # after the update: the copies carry the new opacity and scale
                 t[dead_idx] = t[src]
-        rows = torch.cat([src, dead_idx])
-        for g in self.opt.names:
-            self.opt.exp_avg[g][rows] = 0
-            self.opt.exp_avg_sq[g][rows] = 0
+            elif kind == MOMENT:
+                t[restart] = 0
+            return t  # the statistics: kept
+
+        # in place: the row set and every tensor stay, so there is nothing to install and the exchange step stays bound
+        self._rows().map(relocate)
         self._filter3d = None  # positions changed
         return k
 
@@ -642,15 +632,16 @@ class Trainer:
         ops.mcmc_relocate(self.params["opacity"], self.params["scale"], counts, float(c["mcmc_min_opacity"]))
         src = samples.long()
 
-        def moments(t):
-            t = torch.cat([t, torch.zeros((k,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)], 0)
+        def grow(kind, name, t):  # -> [old | copies of src]
+            if kind == PARAM:
+                return torch.cat([t, t[src]], 0)
+            if kind == STAT:  # zero: no step of the mode reads the statistics
+                return t.new_zeros(n + k)
+            t = torch.cat([t, t.new_zeros((k,) + tuple(t.shape[1:]))], 0)
             t[src] = 0
             return t
 
-        m = ({g: moments(self.opt.exp_avg[g]) for g in self.opt.names},
-             {g: moments(self.opt.exp_avg_sq[g]) for g in self.opt.names})
-        self.params = {g: torch.cat([t, t[src]], 0).contiguous() for g, t in self.params.items()}
-        self._new_optimizer(m)
+        self._install(self._rows().map(grow))
         self._context_for(n + k)
         return k
 
@@ -663,15 +654,8 @@ class Trainer:
         codes = torch.empty(n, dtype=torch.int64, device=xyz.device)
         ops.compute_morton_codes(n, xyz, hi[0], hi[1], hi[2], lo[0], lo[1], lo[2], codes)
         order = torch.sort(codes, stable=True).indices.to(torch.int32).contiguous()  # codes use 63 bits: int64 order is unsigned order
-        for g in GROUPS:
-            if self.params[g].numel():
-                self.params[g] = ops.gather_rows(self.params[g], order)
-        m = ({g: ops.gather_rows(self.opt.exp_avg[g], order) for g in self.opt.names},
-             {g: ops.gather_rows(self.opt.exp_avg_sq[g], order) for g in self.opt.names})
-        acc = (self.opt.uv_grad_accum, self.opt.grad_accum_dur)
-        self._new_optimizer(m)
-        self.opt.uv_grad_accum = ops.gather_rows(acc[0], order)
-        self.opt.grad_accum_dur = ops.gather_rows(acc[1].view(torch.float32), order).view(torch.int32)
+        # parameters, moments and statistics alike: every row moves to its place in the order
+        self._install(self._rows().map(lambda kind, name, t: ops.gather_rows(t, order)))
 
     def save_to_ply(self, path, raw=False):
         """With the 3D smoothing filter on, the file holds the FUSED scale and opacity (ops.filter3d_apply: what the run
