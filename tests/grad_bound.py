@@ -13,7 +13,11 @@ array (tests/test_grad_bound_cpu.py keeps the tables); a GPU array is held to K 
 exchange tests use -- the HIP kernels and the oracle each carry that rounding and may differ in order.
 
 The input condition: an element with borderline > LOOSE_RATIO * unit is held to a loose bar; at most LOOSE_SHARE of a
-scene's live elements may be such."""
+scene's live elements may be such.
+
+The same bar holds the forward's arrays (tests/forward_reference.py, tests/test_forward_bound_*.py): there an element is an
+entry of a per-gaussian array or a pixel's channel, unit its float32 running error from the float32 inputs, borderline
+what the pixel's pairs on the 1/255 threshold and its stop decision are worth; rows = gaussians or pixels."""
 import numpy as np
 
 U = 2.0 ** -24
