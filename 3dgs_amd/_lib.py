@@ -221,6 +221,10 @@ SIGNATURES = {
                                          ctypes.POINTER(Gradients), _P]),
     "gsplat_distortion_loss": (_I, [_P, _P, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P]),
     "gsplat_depth_prior_loss": (_I, [_P, _P, _I, _I, _F, _I, _P, _P, _P]),
+    "gsplat_depth_to_normal": (_I, [_P, _P, _I, _I, _F, _F, _F, _F, _I, _F, _P, _P]),
+    "gsplat_depth_to_normal_backward": (_I, [_P, _P, _I, _I, _F, _F, _F, _F, _I, _F, _P, _I, _P, _P, _P]),
+    "gsplat_normal_prior_loss": (_I, [_P, _P, _I, _I, _F, _I, _P, _P, _P]),
+    "gsplat_normal_smoothness_loss": (_I, [_P, _P, _I, _I, _F, _F, _I, _P, _P, _P]),
     "gsplat_backward_gaussians_camera": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _I,
                                               ctypes.POINTER(Gradients), _P, _P, _P]),
     "gsplat_backward_pass_camera": (_I, [_P, ctypes.POINTER(Gaussians), ctypes.POINTER(Camera), _P, _P, _P, _F, _I,

@@ -22,6 +22,7 @@
 #include "gs_common.h"
 #include "gs_render.h"
 #include "gs_math.h"
+#include "gs_regloss.h"
 
 namespace {
 
@@ -307,24 +308,13 @@ __global__ __launch_bounds__(256) void mse_kernel(long long n, const float *__re
 
 // ---- the depth regularisers (gsplat_distortion_loss, gsplat_depth_prior_loss): plain grid-stride kernels over the [H,W]
 // maps.  Per pixel everything is evaluated in double from the float maps and rounded to float once; the loss is summed in
-// double, per block into `partial` (null: no value asked for) and by reg_loss_finish_kernel in a fixed order.
-constexpr int kRegBlocks = 256;
-
-__device__ __forceinline__ void block_partial(double v, double *__restrict__ partial) {
-  __shared__ double s_wave[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-}
-
-template <bool kAdd>
-__device__ __forceinline__ void put_grad(float *__restrict__ g, long long i, double v) {
-  if (!g) return;
-  if constexpr (kAdd) g[i] += (float)v;
-  else g[i] = (float)v;
-}
+// double, per block into `partial` (null: no value asked for) and by reg_loss_finish_kernel in a fixed order
+// (gs_regloss.h, shared with the normal map's losses in gs_normal.hip).
+using gs::block_partial;
+using gs::kRegBlocks;
+using gs::put_grad;
+using gs::reg_blocks;
+using gs::reg_loss_finish_kernel;
 
 // A = 1 - T, loss(p) = A Q - D^2, partials (Q, -2 D, A); `scale` = weight / P
 template <bool kAdd>
@@ -357,16 +347,6 @@ __global__ __launch_bounds__(256) void depth_prior_loss_kernel(long long n, cons
     put_grad<kAdd>(grad_depth, i, diff > 0.0 ? scale : diff < 0.0 ? -scale : 0.0);
   }
   if (partial) block_partial(sum, partial);
-}
-
-// one wave: the blocks' partial sums in a fixed order, x scale, as the one float of the loss
-__global__ __launch_bounds__(64) void reg_loss_finish_kernel(const double *__restrict__ partial, int n, double scale,
-                                                             float *__restrict__ loss_out) {
-  double v = 0.0;
-  for (int i = threadIdx.x; i < n; i += 64) v += partial[i];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if (threadIdx.x == 0) *loss_out = (float)(scale * v);
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(long long n, float *__restrict__ param,
@@ -646,9 +626,6 @@ int gsplat_fused_loss(const float *predicted_data, const float *gt_data, int row
   }
   return GSPLAT_OK;
 }
-
-// what the two regularisers share behind their kernel: the blocks' partial sums -> loss_out
-static int reg_blocks(long long n) { return (int)std::min<long long>(kRegBlocks, (n + 255) / 256); }
 
 int gsplat_distortion_loss(const float *T, const float *depth, const float *depth2, int rows, int cols, float weight,
                            int accumulate, float *grad_alpha, float *grad_depth, float *grad_depth2, float *loss_out,

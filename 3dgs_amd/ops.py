@@ -190,6 +190,104 @@ def depth_prior_loss(depth, target, weight, grad_depth, accumulate=False, blocki
     return float(out.item()) if blocking else None
 
 
+def _map3(t, name, shape=None):
+    """An [H,W,3] float32 device map (a normal map, an image or a gradient of either); None stays None."""
+    if t is None:
+        return None
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+            or t.dim() != 3 or t.shape[2] != 3 or (shape is not None and tuple(t.shape[:2]) != tuple(shape))):
+        raise ValueError(f"{name} must be a contiguous [H,W,3] float32 device tensor" + (f" of size {tuple(shape)}" if shape else ""))
+    return t
+
+
+def pixel_intrinsics(cam):
+    """(fx, fy, cx, cy) in pixels of a camera dict (scene.make_camera, app.camera_from_colmap, raster.device_camera), such
+    that project_to_screen of z ((x - cx) / fx, (y - cy) / fy, 1) is the pixel (x, y) -- which the compositor samples at
+    its integer coordinate: fx = proj[0] W / 2, cx = (proj[2] + 1) W / 2, and the same in y.  Python floats that are
+    float32 values, as the C ABI takes them."""
+    import numpy as np
+    proj = cam["proj"]
+    proj = (proj.detach().cpu().numpy() if isinstance(proj, torch.Tensor) else np.asarray(proj)).astype(np.float64).reshape(-1)
+    W, H = float(cam["width"]), float(cam["height"])
+    vals = (proj[0] * W / 2.0, proj[5] * H / 2.0, (proj[2] + 1.0) * W / 2.0, (proj[6] + 1.0) * H / 2.0)
+    return tuple(float(np.float32(v)) for v in vals)
+
+
+def _stencil_args(fwd, cam, inverse, alpha_min):
+    """What depth_to_normal and its backward check before any launch -> (depth, T, H, W, fx, fy, cx, cy, inverse, alpha_min)."""
+    import math
+    if "depth" not in fwd:
+        raise ValueError("the forward did not render depth (RasterContext.set_depth(True))")
+    T = _map(fwd["T"], "T")
+    H, W = T.shape
+    depth = _map(fwd["depth"], "depth", (H, W))
+    intr = cam if isinstance(cam, (tuple, list)) else pixel_intrinsics(cam)
+    if len(intr) != 4 or not all(math.isfinite(v) for v in intr) or intr[0] == 0 or intr[1] == 0:
+        raise ValueError("the pixel intrinsics (fx, fy, cx, cy) must be finite, fx and fy not 0")
+    if not (0.0 < float(alpha_min) <= 1.0):
+        raise ValueError("alpha_min must lie in (0, 1]")
+    return (_p(depth), _p(T), int(H), int(W)) + tuple(float(v) for v in intr) + (int(bool(inverse)), float(alpha_min))
+
+
+def depth_to_normal(fwd, cam, inverse, alpha_min=0.5, out=None):
+    """The [H,W,3] normal map of a depth-mode forward (gsplat_depth_to_normal): camera coordinates, facing the camera, from
+    central differences of the back-projected expected depth z = fwd["depth"] / (1 - fwd["T"]) (`inverse`: the forward
+    composited 1/z, RasterContext.set_depth(True, inverse=True)).  A pixel without a normal -- the border, an opacity
+    below alpha_min at it or at one of its four neighbours -- is (0,0,0).  cam: a camera dict, or (fx, fy, cx, cy) as
+    pixel_intrinsics gives them.  out: the map to write, or None for a new one."""
+    args = _stencil_args(fwd, cam, inverse, alpha_min)
+    H, W = args[2], args[3]
+    if out is None:
+        out = torch.empty(H, W, 3, dtype=torch.float32, device=fwd["T"].device)
+    check(_lib.load().gsplat_depth_to_normal(*args, _p(_map3(out, "out", (H, W))), _stream()))
+    return out
+
+
+def depth_to_normal_backward(fwd, cam, inverse, grad_normal, grad_depth, grad_alpha, alpha_min=0.5, accumulate=False):
+    """dL/d normal ([H,W,3]) of depth_to_normal's map -> grad_depth = dL/d fwd["depth"] and grad_alpha = dL/d(1 - fwd["T"])
+    ([H,W] maps as the backwards take them; either may be None), overwritten or, with accumulate=True, added to
+    (gsplat_depth_to_normal_backward)."""
+    args = _stencil_args(fwd, cam, inverse, alpha_min)
+    H, W = args[2], args[3]
+    if grad_normal is None:
+        raise ValueError("grad_normal is required")
+    check(_lib.load().gsplat_depth_to_normal_backward(
+        *args, _p(_map3(grad_normal, "grad_normal", (H, W))), int(bool(accumulate)),
+        _p(_map(grad_depth, "grad_depth", (H, W))), _p(_map(grad_alpha, "grad_alpha", (H, W))), _stream()))
+
+
+def normal_prior_loss(normal, prior, weight, grad_normal, accumulate=False, blocking=False):
+    """weight x mean over all H x W pixels of 1 - n . prior / |prior| on the pixels with a normal and a non-zero prior
+    ([H,W,3], camera coordinates); grad_normal ([H,W,3] or None) gets -weight / P x prior / |prior| there and 0 elsewhere,
+    overwritten or added to (gsplat_normal_prior_loss).  blocking=True returns the loss (a read-back), otherwise None."""
+    normal = _map3(normal, "normal")
+    if prior is None:
+        raise ValueError("prior is required")
+    H, W = normal.shape[:2]
+    out = torch.empty(1, dtype=torch.float32, device=normal.device) if blocking else None
+    check(_lib.load().gsplat_normal_prior_loss(_p(normal), _p(_map3(prior, "prior", (H, W))), int(H), int(W), float(weight),
+                                               int(bool(accumulate)), _p(_map3(grad_normal, "grad_normal", (H, W))),
+                                               _p(out), _stream()))
+    return float(out.item()) if blocking else None
+
+
+def normal_smoothness_loss(normal, image, weight, grad_normal, edge_scale=1.0, accumulate=False, blocking=False):
+    """weight x (1 / P) x the sum over the horizontally or vertically adjacent pairs of pixels with a normal of
+    w sum_c |n_a,c - n_b,c|, w = exp(-edge_scale x mean_c |I_a,c - I_b,c|) for `image` ([H,W,3], a constant) or 1 when it is
+    None; grad_normal ([H,W,3] or None) gets the subgradient (sign(0) = 0), overwritten or added to
+    (gsplat_normal_smoothness_loss).  blocking=True returns the loss (a read-back), otherwise None."""
+    import math
+    normal = _map3(normal, "normal")
+    H, W = normal.shape[:2]
+    if not math.isfinite(float(edge_scale)):
+        raise ValueError("edge_scale must be finite")
+    out = torch.empty(1, dtype=torch.float32, device=normal.device) if blocking else None
+    check(_lib.load().gsplat_normal_smoothness_loss(_p(normal), _p(_map3(image, "image", (H, W))), int(H), int(W),
+                                                    float(weight), float(edge_scale), int(bool(accumulate)),
+                                                    _p(_map3(grad_normal, "grad_normal", (H, W))), _p(out), _stream()))
+    return float(out.item()) if blocking else None
+
+
 def compute_psnr(predicted_data, gt_data, rows, cols):
     out = ctypes.c_float(0.0)
     check(_lib.load().gsplat_compute_psnr(_p(predicted_data), _p(gt_data), rows, cols, ctypes.byref(out), _stream()))

@@ -22,6 +22,8 @@ from .optimizer import AdamOptimizer, DEFAULT_LR
 from .rows import MOMENT, PARAM, STAT, RowTable
 
 DISTORTION_WEIGHT = 10.0  # the default of config key distortion_weight (README, "Depth regularisers")
+NORMAL_PRIOR_WEIGHT = 0.2   # the defaults of config keys normal_prior_weight and normal_smooth_weight: README, "Normal
+NORMAL_SMOOTH_WEIGHT = 0.2  # maps from rendered depth", has the numbers they come from
 
 # config/base.yaml of the reference: the keys the loop reads
 DEFAULT_CONFIG = dict(
@@ -68,7 +70,20 @@ DEFAULT_CONFIG = dict(
     # With either key the context renders depth (RasterContext.set_depth, inverse as distortion_inverse, the second
     # moment only with distortion).  One rank only; distortion has no absgrad form.
     distortion=False, distortion_weight=DISTORTION_WEIGHT, distortion_start=3000, distortion_inverse=True,
-    depth_prior=False, depth_prior_weight_init=1.0, depth_prior_weight_final=0.01)
+    depth_prior=False, depth_prior_weight_init=1.0, depth_prior_weight_final=0.01,
+    # normal_prior / normal_smooth: from iteration normal_start on every step derives the normal map of the rendered depth
+    # (ops.depth_to_normal: central differences of the back-projected expected depth; no normal where the opacity of a
+    # pixel or of one of its four neighbours is below normal_alpha_min) and adds
+    #   normal_prior:  normal_prior_weight x the mean of 1 - n . prior / |prior| for a view given as (camera, image, depth
+    #                  target or None, prior) -- prior an [H,W,3] float32 device tensor of camera-space normals facing the
+    #                  camera, zero where there is no data (ops.normal_prior_loss); views without one skip the term;
+    #   normal_smooth: normal_smooth_weight x the mean over adjacent pixel pairs of exp(-normal_edge_scale x the mean
+    #                  absolute colour difference of the ground truth) x |n_a - n_b|_1 (ops.normal_smoothness_loss:
+    #                  DN-Splatter's edge-aware form).
+    # Their gradient goes through ops.depth_to_normal_backward into the depth and opacity maps' gradients, beside the two
+    # terms above.  The context renders depth as for those (inverse as distortion_inverse).  One rank only.
+    normal_prior=False, normal_prior_weight=NORMAL_PRIOR_WEIGHT, normal_smooth=False,
+    normal_smooth_weight=NORMAL_SMOOTH_WEIGHT, normal_edge_scale=1.0, normal_start=3000, normal_alpha_min=0.5)
 
 
 def _logit(p):
@@ -110,7 +125,8 @@ def draw_view_indices(rng, iteration, world, num_views):
 class Trainer:
     """params: dict of device tensors (xyz rgb opacity scale quaternion, optionally sh) as gsplat_initialize_gaussians
     returns them; views: list of (camera dict for raster.device_camera, ground-truth image tensor [H,W,3] on device) or,
-    for config key depth_prior, (camera, image, inverse-depth target [H,W] float32 on device)."""
+    for config key depth_prior, (camera, image, inverse-depth target [H,W] float32 on device) or, for config key
+    normal_prior, (camera, image, that target or None, normal prior [H,W,3] float32 on device)."""
 
     def __init__(self, params, views, config=None, scene_extent=1.0, seed=0, exchange="split", comm=None):
         """With an initialised torch.distributed group of W > 1 ranks the loop is view-sharded: every
@@ -150,7 +166,11 @@ class Trainer:
             if self.cfg["distortion"] and self.cfg["absgrad"]:
                 raise ValueError("distortion has no absgrad form: the compositing backward refuses the second moment's "
                                  "gradient in absgrad mode")
+        if (self.cfg["normal_prior"] or self.cfg["normal_smooth"]) and self.world > 1:
+            raise ValueError("normal_prior / normal_smooth train on one rank: the view-sharded step takes no depth gradients")
         self._depth_maps = {}  # (H, W) -> the three gradient maps (dL/d alpha, dL/d depth, dL/d depth2), allocated once
+        self._normal_maps = {}  # (H, W) -> (normal map, dL/d normal), [H,W,3] each, allocated once (normal_prior / _smooth)
+        self._intrinsics = {}   # id(camera dict) -> (camera, ops.pixel_intrinsics of it): read from the device once
         self.last_regularisers = {}  # what the last train_step added: name -> weight
         self._filter3d = None       # [N] device tensor of the current gaussians; None: to be (re)computed
         self._filter3d_cams = None  # the training views' device camera arrays, built once
@@ -209,7 +229,7 @@ class Trainer:
         ctx.set_lean_forward(True)  # the loop only runs the fused backward, which recomputes Sigma / J / conic
         ctx.set_absgrad(bool(self.cfg["absgrad"]))
         ctx.set_antialiased(bool(self.cfg["antialiased"]))
-        if self.cfg["distortion"] or self.cfg["depth_prior"]:  # (both off: the context is never put in depth mode)
+        if self._depth_keys():  # (all off: the context is never put in depth mode)
             ctx.set_depth(True, inverse=bool(self.cfg["distortion_inverse"]), moment=bool(self.cfg["distortion"]))
         return ctx
 
@@ -266,6 +286,17 @@ class Trainer:
             self._grads2 = (n, dict(xyz=torch.empty(n, 3, device=dev), precompute_rgb=torch.empty(n, 3, device=dev)))
         return {k: v[:m] for k, v in self._grads2[1].items()}
 
+    def _depth_keys(self):
+        """Whether any term on the depth maps is configured: the context then renders depth."""
+        c = self.cfg
+        return bool(c["distortion"] or c["depth_prior"] or c["normal_prior"] or c["normal_smooth"])
+
+    def _intrinsics_of(self, cam):
+        hit = self._intrinsics.get(id(cam))
+        if hit is None or hit[0] is not cam:
+            hit = self._intrinsics[id(cam)] = (cam, ops.pixel_intrinsics(cam))
+        return hit[1]
+
     def depth_prior_weight(self, it):
         """The depth prior's weight at iteration `it`: exponential from depth_prior_weight_init to depth_prior_weight_final
         over num_iters."""
@@ -273,15 +304,18 @@ class Trainer:
         w0, w1 = float(c["depth_prior_weight_init"]), float(c["depth_prior_weight_final"])
         return w0 * (w1 / w0) ** (float(it) / float(c["num_iters"]))
 
-    def _depth_regularisers(self, fwd, it, H, W, depth_target):
-        """The depth terms of this iteration (config keys distortion, depth_prior), evaluated into the three reusable
-        [H,W] maps: dict(grad_alpha=, grad_depth=, grad_depth2=) for the backward -- empty when no term is active, and
-        then nothing here launches anything."""
+    def _depth_regularisers(self, fwd, it, H, W, depth_target, cam=None, gt_image=None, normal_target=None):
+        """The depth terms of this iteration (config keys distortion, depth_prior, normal_prior, normal_smooth), evaluated
+        into the three reusable [H,W] maps: dict(grad_alpha=, grad_depth=, grad_depth2=) for the backward -- empty when no
+        term is active, and then nothing here launches anything."""
         c = self.cfg
         self.last_regularisers = {}
         distortion = bool(c["distortion"]) and it >= int(c["distortion_start"])
         prior = bool(c["depth_prior"]) and depth_target is not None
-        if not (distortion or prior):
+        normals = it >= int(c["normal_start"])
+        n_prior = normals and bool(c["normal_prior"]) and normal_target is not None
+        n_smooth = normals and bool(c["normal_smooth"])
+        if not (distortion or prior or n_prior or n_smooth):
             return {}
         maps = self._depth_maps.get((H, W))
         if maps is None:
@@ -299,6 +333,29 @@ class Trainer:
             ops.depth_prior_loss(fwd["depth"], depth_target, w, g_depth, accumulate=distortion)
             out["grad_depth"] = g_depth
             self.last_regularisers["depth_prior"] = w
+        if n_prior or n_smooth:
+            nmaps = self._normal_maps.get((H, W))
+            if nmaps is None:
+                dev = fwd["T"].device
+                nmaps = self._normal_maps[(H, W)] = tuple(torch.empty(H, W, 3, dtype=torch.float32, device=dev) for _ in range(2))
+            normal, g_normal = nmaps
+            intr, inverse, a_min = self._intrinsics_of(cam), bool(c["distortion_inverse"]), float(c["normal_alpha_min"])
+            ops.depth_to_normal(fwd, intr, inverse, alpha_min=a_min, out=normal)
+            if n_prior:
+                w = float(c["normal_prior_weight"])
+                ops.normal_prior_loss(normal, normal_target, w, g_normal)
+                self.last_regularisers["normal_prior"] = w
+            if n_smooth:
+                w = float(c["normal_smooth_weight"])
+                ops.normal_smoothness_loss(normal, gt_image, w, g_normal, edge_scale=float(c["normal_edge_scale"]),
+                                           accumulate=n_prior)
+                self.last_regularisers["normal_smooth"] = w
+            # added to what distortion / the depth prior wrote; a map neither wrote starts from zero
+            if (distortion or prior) and "grad_alpha" not in out:
+                g_alpha.zero_()
+            ops.depth_to_normal_backward(fwd, intr, inverse, g_normal, g_depth, g_alpha, alpha_min=a_min,
+                                         accumulate=distortion or prior)
+            out["grad_depth"], out["grad_alpha"] = g_depth, g_alpha
         return out
 
     def _begin_step(self):
@@ -312,8 +369,9 @@ class Trainer:
         self._refresh_filter3d(it)
         return it, bg, self._context_for(self.num_gaussians)
 
-    def train_step(self, cam, gt_image, want_loss=True, depth_target=None):
-        """depth_target: this view's inverse-depth prior (config key depth_prior), or None."""
+    def train_step(self, cam, gt_image, want_loss=True, depth_target=None, normal_target=None):
+        """depth_target: this view's inverse-depth prior (config key depth_prior), or None; normal_target: its normal prior
+        (config key normal_prior), or None."""
         if self.world > 1:
             return self._train_step_sharded(cam, gt_image, want_loss)
         c = self.cfg
@@ -330,9 +388,11 @@ class Trainer:
         grad_image = self._grad_image_for(H, W, gt_image.device)
         # the loss value is a blocking read-back: only fetched when the caller logs it
         loss = ops.fused_loss(fwd["image"], gt_image, H, W, float(c["ssim_frac"]), grad_image, blocking=want_loss)
-        # the depth terms (config keys distortion, depth_prior; {} when none is active: the plain backward, exactly) ride
-        # with whichever backward the iteration runs -- the Adam-inside forms take the depth row as it is
-        dmaps = self._depth_regularisers(fwd, it, H, W, depth_target) if (c["distortion"] or c["depth_prior"]) else {}
+        # the depth terms (config keys distortion, depth_prior, normal_prior, normal_smooth; {} when none is active: the
+        # plain backward, exactly) ride with whichever backward the iteration runs -- the Adam-inside forms take the depth
+        # row as it is
+        dmaps = self._depth_regularisers(fwd, it, H, W, depth_target, cam, gt_image, normal_target) \
+            if self._depth_keys() else {}
         fused_adam = self.fused_adam  # (0 with antialiased, filter3d or mcmc: decided in __init__)
         if fused_adam == 3:
             # r06: the SH group's step in a kernel that reads the coefficient rows once (update + the sums the position
@@ -425,10 +485,13 @@ class Trainer:
         for _ in range(num_iters):
             v = self.draw_views()[self.rank]
             cam, gt = self.views[v][:2]
-            target = self.views[v][2] if len(self.views[v]) > 2 else None  # (config key depth_prior)
+            extra = {}  # (config keys depth_prior, normal_prior: passed only when the view has one)
+            if len(self.views[v]) > 2 and self.views[v][2] is not None:
+                extra["depth_target"] = self.views[v][2]
+            if len(self.views[v]) > 3 and self.views[v][3] is not None:
+                extra["normal_target"] = self.views[v][3]
             want = bool(loss_every) and (self.iter % loss_every == 0 or (log_every and (self.iter + 1) % log_every == 0))
-            loss = self.train_step(cam, gt, want_loss=want, depth_target=target) if target is not None else \
-                self.train_step(cam, gt, want_loss=want)
+            loss = self.train_step(cam, gt, want_loss=want, **extra)
             if eval_every and (self.iter - 1) % eval_every == 0 and eval_views:
                 psnr = self.evaluate(eval_views)
                 if on_eval:
@@ -453,6 +516,25 @@ class Trainer:
         finally:
             ctx.set_render_only(False)
         return total / len(views)
+
+    def render_normals(self, cam, alpha_min=None):
+        """The [H,W,3] normal map of the current gaussians from `cam` (ops.depth_to_normal on a render-only forward at
+        background 0, in the mode the run trains in): camera coordinates, facing the camera, (0,0,0) where there is none.
+        alpha_min: config key normal_alpha_min unless given."""
+        ctx = self._context_for(self.num_gaussians)
+        inverse = bool(self.cfg["distortion_inverse"])
+        mode = (ctx._depth, ctx._depth_inverse, ctx._depth_moment)
+        ctx.set_render_only(True)
+        try:
+            if not mode[0]:  # a run without depth terms: depth mode for this forward only
+                ctx.set_depth(True, inverse=inverse)
+            fwd = ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
+            return ops.depth_to_normal(fwd, self._intrinsics_of(cam), inverse if not mode[0] else mode[1],
+                                       alpha_min=float(self.cfg["normal_alpha_min"] if alpha_min is None else alpha_min))
+        finally:
+            if not mode[0]:
+                ctx.set_depth(False)
+            ctx.set_render_only(False)
 
     def contribution_scores(self, views=None):
         """dict(weight_sum, weight_max, pixels): [N] device tensors, the blend-weight statistics of every gaussian

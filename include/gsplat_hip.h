@@ -577,6 +577,42 @@ int gsplat_distortion_loss(const float *T, const float *depth, const float *dept
 int gsplat_depth_prior_loss(const float *depth, const float *target, int rows, int cols, float weight, int accumulate,
                             float *grad_depth, float *loss_out, void *stream);
 
+/* Normal maps from the rendered depth, and two losses on them (no ABI bump: new entry points only; gs_normal.hip).  Every
+ * map is [rows, cols] (x 3 for a normal, an image or their gradients) float on the device; every pixel is evaluated in
+ * double from the float inputs and rounded to float once; every kernel gathers (a thread owns an output pixel, no
+ * atomics), so two runs give the same bits.
+ *   With A = 1 - T, a pixel is `ok` when A >= alpha_min, depth > 0 and both are finite; its expected depth is
+ *   z = depth / A (inverse: A / depth) and its point P = z ((x - cx) / fx, (y - cy) / fy, 1) with x, y the INTEGER pixel
+ *   coordinates (where the compositor samples).  At an interior pixel tx = P(x+1,y) - P(x-1,y), ty = P(x,y+1) - P(x,y-1),
+ *   c = ty x tx, n = c / |c|: camera coordinates, facing the camera (a fronto-parallel surface: (0,0,-1)).  The normal is
+ *   valid when the pixel and its four neighbours are ok and |c| > 0; every other pixel, the one-pixel border included,
+ *   gets (0,0,0) exactly -- the "no normal" marker of the losses below.
+ *   gsplat_depth_to_normal           writes normal [rows, cols, 3];
+ *   gsplat_depth_to_normal_backward  from grad_normal = dL/dn ([rows, cols, 3]) to grad_depth = dL/d depth and grad_alpha =
+ *                                    dL/d(1 - T) (what every backward here takes), through n = c / |c|, the cross product,
+ *                                    P and z(depth, A).  A pixel's depth enters the normals of its four neighbours only; a
+ *                                    pixel no valid normal reads gets 0 exactly.  Either output may be NULL; overwritten,
+ *                                    or added to when `accumulate` is set;
+ *   gsplat_normal_prior_loss         weight / P x sum over the pixels with a non-zero normal AND a non-zero prior of
+ *                                    1 - n . prior / |prior| (P = rows x cols); grad_normal gets -weight / P x prior / |prior|
+ *                                    there and 0 elsewhere;
+ *   gsplat_normal_smoothness_loss    weight / P x sum over the horizontally or vertically adjacent pairs (a, b) of non-zero
+ *                                    normals of w_ab sum_c |n_a,c - n_b,c|, w_ab = exp(-edge_scale x mean_c |I_a,c - I_b,c|)
+ *                                    for an image I [rows, cols, 3] (a constant: no gradient), 1 when image is NULL;
+ *                                    grad_normal gets the subgradient with sign(0) = 0.
+ *   grad_normal of the two losses may be NULL and follows `accumulate`; loss_out may be NULL, given it is a device float
+ *   overwritten with the sum reduced in double in a fixed order.  Refused with GSPLAT_ERR_INVALID_ARG before anything is
+ *   launched: non-positive sizes, alpha_min outside (0, 1], non-finite intrinsics, fx or fy equal to 0. */
+int gsplat_depth_to_normal(const float *depth, const float *T, int rows, int cols, float fx, float fy, float cx, float cy,
+                           int inverse, float alpha_min, float *normal, void *stream);
+int gsplat_depth_to_normal_backward(const float *depth, const float *T, int rows, int cols, float fx, float fy, float cx,
+                                    float cy, int inverse, float alpha_min, const float *grad_normal, int accumulate,
+                                    float *grad_depth, float *grad_alpha, void *stream);
+int gsplat_normal_prior_loss(const float *normal, const float *prior, int rows, int cols, float weight, int accumulate,
+                             float *grad_normal, float *loss_out, void *stream);
+int gsplat_normal_smoothness_loss(const float *normal, const float *image, int rows, int cols, float weight,
+                                  float edge_scale, int accumulate, float *grad_normal, float *loss_out, void *stream);
+
 /* Camera gradient (no ABI bump: new entry points only).  view (camera->view[0..11] = [R|t]) and campos are two
  * independent inputs, as the forward reads them.  With c_j = dL/d xyz_c of visible gaussian j (projection, screen and
  * depth terms), p_j its world position, dM_j = dL/dM for M = J R and s_j its position gradient through the SH view
