@@ -222,6 +222,31 @@ int gsplat_context_accumulate_contributions(gsplat_context *c, int num_gaussians
                                   (hipStream_t)stream);
 }
 
+int gsplat_context_render_features(gsplat_context *c, int num_gaussians, int channels, const float *features, float *out,
+                                   void *stream) {
+  // (every check before the launch: a refused call leaves the caller's arrays as they were)
+  GS_REQUIRE(c != nullptr, "null context");
+  GS_REQUIRE(c->lists_ready, "no forward pass recorded in this context");
+  GS_REQUIRE(num_gaussians == c->N, "does not match the recorded forward");
+  GS_REQUIRE(channels >= 1 && channels <= 512, "channels must be 1 .. 512");
+  GS_REQUIRE_DEV(features);
+  GS_REQUIRE_DEV(out);
+  return gs::launch_features_fwd(c->recs.as<float4>(), c->sorted.as<int>(), c->ranges.as<int>(), c->n_px.as<int>(),
+                                 c->c2g.as<int>(), c->width, c->height, channels, features, out, (hipStream_t)stream);
+}
+
+int gsplat_context_lift_features(gsplat_context *c, int num_gaussians, int channels, const float *map, float *lifted,
+                                 void *stream) {
+  GS_REQUIRE(c != nullptr, "null context");
+  GS_REQUIRE(c->lists_ready, "no forward pass recorded in this context");
+  GS_REQUIRE(num_gaussians == c->N, "does not match the recorded forward");
+  GS_REQUIRE(channels >= 1 && channels <= 512, "channels must be 1 .. 512");
+  GS_REQUIRE_DEV(map);
+  GS_REQUIRE_DEV(lifted);
+  return gs::launch_features_lift(c->recs.as<float4>(), c->sorted.as<int>(), c->ranges.as<int>(), c->n_px.as<int>(),
+                                  c->c2g.as<int>(), c->width, c->height, channels, map, lifted, (hipStream_t)stream);
+}
+
 int gsplat_context_depth_map(gsplat_context *c, const float **depth) {
   GS_REQUIRE(c && depth, "null argument");
   *depth = nullptr;

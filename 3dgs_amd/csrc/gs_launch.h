@@ -53,6 +53,12 @@ int launch_fwd_segments_table(const int *ranges, int num_tiles, const FwdSegment
 int launch_tile_segments(const int *ranges, const int *tops, int num_tiles, const TileSegments &seg, hipStream_t st);
 int launch_contributions(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
                          int width, int height, float *weight_sum, float *weight_max, int *pixels, hipStream_t st);
+// the caller's channels through the recorded forward's weights and back (features_fwd_kernel, features_lift_kernel):
+// features [N,C] in global order -> out [H,W,C]; map [H,W,C] -> lifted [N,C] in global order, accumulated into
+int launch_features_fwd(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
+                        int width, int height, int channels, const float *features, float *out, hipStream_t st);
+int launch_features_lift(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
+                         int width, int height, int channels, const float *map, float *lifted, hipStream_t st);
 int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
 bool tile_order_supported(int num_tiles);
 

@@ -1950,6 +1950,278 @@ __global__ __launch_bounds__(256) void contributions_kernel(const float4 *__rest
   }
 }
 
+// ---- feature maps of a recorded forward (gsplat_context_render_features, gsplat_context_lift_features) ---------------
+// The walk of contributions_kernel twice more, for the caller's own per-gaussian channels f[N,C] (global order) and its
+// adjoint.  With w_ip = alpha * T(before) of entry i of the tile's list at pixel p, over the entries the forward
+// composited (i < n(p), alpha > 1/255 -- the same load_record / block_hits / stage_record / row lists, so the same
+// (gaussian, block) pairs, and alpha and T bit for bit as there):
+//   render   out[p, c]     = sum_i w_ip f[g_i, c]          (features_fwd_kernel)
+//   lift     lifted[g, c] += sum_p w_gp map[p, c]          (features_lift_kernel)
+// No background term on either side (the caller has T), nothing of the geometry is differentiated.
+// Channels are taken in chunks of K = 4, 8 or 16 (one K per launch: the smallest that holds C, 16 beyond); gridDim.y
+// counts the chunks, every chunk walks the tile's list again.  Outside pixels of partial tiles carry T = 0, read and
+// write nothing.  A list longer than kSegSplitMin is walked whole by the one workgroup, as in contributions_kernel.
+//
+// features_fwd_kernel: per batch, beside the records, the workgroup gathers the chunk's slice of the batch's feature rows
+// into LDS -- (slot, channel) spread over all 256 threads, so the K channels of a row are one coalesced read; every
+// thread finds its row through sorted and compact_to_global itself, which keeps the gather in front of the batch's one
+// staging barrier -- and per trip a lane does acc[c] = fma(w, s_feat[slot][c], acc[c]) on K/4 16-byte reads (the 16 lanes
+// of a row read one address: a broadcast).  A pixel's sum runs in list order, one chain per channel, without atomics: the
+// map carries the same bits in every run, under either binning route, at every C and after every kind of forward whose
+// list was walked whole -- channel c of the forward's own colours IS the forward's image at background 0.
+//
+// features_lift_kernel: the lane holds its pixel's K map values.  Per trip the row's 16 x K products w map[p, c] are
+// reduced over the row by a transposed butterfly on DPP (row_transpose_sum: 47 VALU at K = 16, the products included, against 80 for K products and K row_sums)
+// that leaves lane j with channel j's row total, so ONE ds_add_f64 per wave and trip adds all K totals of the four rows'
+// (gaussian, block) pairs into the batch's LDS accumulators [slot][K] (doubles: see there); behind the batch thread (slot, c) sends every
+// non-zero total to lifted[compact_to_global[id], c]: one global float atomic per (tile, gaussian, channel), none for a
+// gaussian no pixel of the tile composited.  Float atomics in arrival order: the lifted sums are order-dependent in
+// their last bits, as the gradient rows and weight_sum are.
+template <int kCtrl>
+__device__ __forceinline__ float dpp_take(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, 0xF, 0xF, false));
+}
+// The row's sums of w m[c], c < K, over its 16 lanes: lane j < K of every 16-lane row ends with channel j's.  Two folding
+// stages inside the quad (lanes 1 and 2 apart: each keeps the half of the values its lane bit selects and takes the
+// partner's partial of the same half, so lane (b1 b0) of a quad ends with the quad's sums of channels 4 i + 2 b1 + b0), two
+// row rotations (by 8 and by 4 lanes: both keep a lane's place in its quad) that add the four quads, and a select of
+// i = the lane's quad.  The first stage selects among the lane's own m, which no trip changes: the caller makes those
+// selects once (transpose_operands: mk = what the lane keeps, ms = what it sends) and the products are formed on the
+// selected halves.
+template <int K>
+__device__ __forceinline__ void transpose_operands(const float (&m)[K], int j, float (&mk)[K / 2], float (&ms)[K / 2]) {
+  const bool b0 = (j & 1) != 0;
+#pragma unroll
+  for (int i = 0; i < K / 2; ++i) {
+    mk[i] = b0 ? m[2 * i + 1] : m[2 * i];
+    ms[i] = b0 ? m[2 * i] : m[2 * i + 1];
+  }
+}
+template <int K>
+__device__ __forceinline__ float row_transpose_sum(float w, const float (&mk)[K / 2], const float (&ms)[K / 2], int j) {
+  const bool b1 = (j & 2) != 0;
+  float u[K / 2], t[K / 4];
+#pragma unroll
+  for (int i = 0; i < K / 2; ++i) u[i] = w * mk[i] + dpp_take<0xB1>(w * ms[i]);  // quad_perm [1,0,3,2]
+#pragma unroll
+  for (int i = 0; i < K / 4; ++i) {
+    const float keep = b1 ? u[2 * i + 1] : u[2 * i], send = b1 ? u[2 * i] : u[2 * i + 1];
+    t[i] = keep + dpp_take<0x4E>(send);  // quad_perm [2,3,0,1]
+    t[i] = dpp_add<0x128>(t[i]);         // row_ror:8
+    t[i] = dpp_add<0x124>(t[i]);         // row_ror:4
+  }
+  float r = t[0];
+  if constexpr (K >= 8) r = (j >> 2) == 1 ? t[1] : r;
+  if constexpr (K >= 16) { r = (j >> 2) == 2 ? t[2] : r; r = (j >> 2) == 3 ? t[3] : r; }
+  return r;
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void features_fwd_kernel(const float4 *__restrict__ recs, const int *__restrict__ sorted,
+                                                           const int *__restrict__ ranges, const int *__restrict__ n_px,
+                                                           const int *__restrict__ c2g, int width, int height, int ntx,
+                                                           int num_tiles, int channels, const float *__restrict__ features,
+                                                           float *__restrict__ out, int vec) {
+  static_assert(K == 4 || K == 8 || K == 16, "chunk widths");
+  constexpr int kQ = K / 4;  // 16-byte reads per feature row
+  __shared__ float4 s_r0[kBatch + 1], s_r1[kBatch + 1];  // as in contributions_kernel; [kBatch]: the sentinel
+  __shared__ float4 s_feat[(kBatch + 1) * kQ];           // [slot][K]; the sentinel's row is zeros
+  __shared__ int s_tile_top;
+  __shared__ __attribute__((aligned(16))) unsigned short s_list[16 * kListStride + 2];
+  const int tile = ordered_tile(nullptr, (int)blockIdx.x, num_tiles);
+  if (tile >= num_tiles) return;
+  const int c0 = (int)blockIdx.y * K;  // (more than one chunk: K = 16)
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, row = lane >> 4, j = lane & 15;
+  if (tid == 0) {
+    s_r0[kBatch] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    s_r1[kBatch] = sentinel_r1();
+    s_tile_top = 0;
+  }
+  if (tid < kQ) s_feat[kBatch * kQ + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const int tile_x = tile % ntx, tile_y = tile / ntx;
+  const int px = tile_x * 16 + (wave & 1) * 8 + (row & 1) * 4 + (j & 3);
+  const int py = tile_y * 16 + (wave >> 1) * 8 + (row >> 1) * 4 + (j >> 2);
+  const bool inside = px < width && py < height;
+  const float fpx = (float)px, fpy = (float)py;
+  const float tx0 = (float)(tile_x * 16), ty0 = (float)(tile_y * 16);
+  const char *r0b = reinterpret_cast<const char *>(s_r0), *r1b = reinterpret_cast<const char *>(s_r1);
+  const char *fb = reinterpret_cast<const char *>(s_feat);
+  float *s_feat_f = reinterpret_cast<float *>(s_feat);
+  const int start = ranges[tile], total = ranges[tile + 1] - start;
+  const int n = inside ? min(n_px[py * width + px], total) : 0;
+  const int row_top = row_max_int(n);
+  const int top0 = __builtin_amdgcn_readlane(row_top, 0), top1 = __builtin_amdgcn_readlane(row_top, 16);
+  const int top2 = __builtin_amdgcn_readlane(row_top, 32), top3 = __builtin_amdgcn_readlane(row_top, 48);
+  __syncthreads();
+  if (lane == 0) atomicMax(&s_tile_top, max(max(top0, top1), max(top2, top3)));
+  __syncthreads();
+  const int top = s_tile_top;
+  const RawSplats none = {nullptr, nullptr, nullptr, nullptr};
+  unsigned short *lists = s_list + wave * 4 * kListStride;
+  const unsigned short *my_list = lists + row * kListStride;
+  float T = inside ? 1.0f : 0.0f;
+  float acc[K];
+#pragma unroll
+  for (int c = 0; c < K; ++c) acc[c] = 0.0f;
+  for (int base = 0; base < top; base += kBatch) {
+    const int count = min(kBatch, top - base);
+    __syncthreads();  // the trips of the batch before have read the records and the feature rows
+    if (tid < count) {
+      const int g = sorted[start + base + tid];
+      SplatRec s = load_record<true>(g, recs, none);
+      const unsigned int hits = block_hits(s, tx0, ty0);
+      stage_record(s);
+      s_r0[tid] = s.r0;
+      s_r1[tid] = make_float4(s.r1.x, s.r1.y, s.r1.y > kLog2AlphaMax ? kLog2AlphaMax : s.r1.y, __uint_as_float(hits));
+    }
+    for (int e = tid; e < count * K; e += 256) {  // (slot, channel) = (e / K, e % K)
+      const int c = c0 + (e & (K - 1));
+      const size_t gi = (size_t)c2g[sorted[start + base + e / K]];
+      s_feat_f[e] = c < channels ? features[gi * (size_t)channels + c] : 0.0f;
+    }
+    __syncthreads();
+    const RowCounts rc = build_row_lists<kListStride>(s_r1, lists, count, wave, lane, top0 - base, top1 - base, top2 - base,
+                                                      top3 - base, 1);
+    const int trips = max(max(rc.c0, rc.c1), max(rc.c2, rc.c3));
+    for (int i = 0; i < trips; ++i) {
+      const int off = my_list[i];  // a row past the end of its list reads the sentinel record: alpha 0, features 0
+      const float4 a = *reinterpret_cast<const float4 *>(r0b + off), b = *reinterpret_cast<const float4 *>(r1b + off);
+      float al = staged_alpha_capped(a.z, a.w, b.x, b.y, b.z, a.x - fpx, a.y - fpy);
+      const bool on = al > kAlphaMin && base + (off >> 4) < n;
+      al = on ? al : 0.0f;
+      const float w = al * T;
+      T = __builtin_fmaf(-al, T, T);
+      const float4 *f = reinterpret_cast<const float4 *>(fb + off * kQ);
+#pragma unroll
+      for (int q = 0; q < kQ; ++q) {
+        const float4 v = f[q];
+        acc[4 * q + 0] = __builtin_fmaf(w, v.x, acc[4 * q + 0]);
+        acc[4 * q + 1] = __builtin_fmaf(w, v.y, acc[4 * q + 1]);
+        acc[4 * q + 2] = __builtin_fmaf(w, v.z, acc[4 * q + 2]);
+        acc[4 * q + 3] = __builtin_fmaf(w, v.w, acc[4 * q + 3]);
+      }
+    }
+  }
+  if (inside) {
+    float *o = out + (size_t)(py * width + px) * (size_t)channels + c0;
+    if (vec) {  // C a multiple of 4 and `out` 16-byte aligned: whole 16-byte stores
+#pragma unroll
+      for (int q = 0; q < kQ; ++q)
+        if (c0 + 4 * q < channels)
+          reinterpret_cast<float4 *>(o)[q] = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < K; ++c)
+        if (c0 + c < channels) o[c] = acc[c];
+    }
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void features_lift_kernel(const float4 *__restrict__ recs, const int *__restrict__ sorted,
+                                                            const int *__restrict__ ranges, const int *__restrict__ n_px,
+                                                            const int *__restrict__ c2g, int width, int height, int ntx,
+                                                            int num_tiles, int channels, const float *__restrict__ map,
+                                                            float *__restrict__ lifted, int vec) {
+  static_assert(K == 4 || K == 8 || K == 16, "chunk widths");
+  __shared__ float4 s_r0[kBatch + 1], s_r1[kBatch + 1];  // as in contributions_kernel; [kBatch]: the sentinel
+  // [slot][K]: the batch's totals; slot kBatch: the sentinel's (rows past the end of their list add zeros there).  Doubles
+  // for the rate of the LDS atomic, as in render_bwd_kernel: ds_add_f32 retires about one lane every three cycles, and
+  // with K lanes of each of a wave's four rows adding in every trip that bounded the kernel (K = 16 at 1080p: 1.22 ms
+  // against 0.29 ms for contributions_kernel's walk); ds_add_f64 runs at LDS rate (profiles/microbench/lds_atomic_rate)
+  __shared__ double s_acc[(kBatch + 1) * K];
+  __shared__ int s_gid[kBatch];
+  __shared__ int s_tile_top;
+  __shared__ __attribute__((aligned(16))) unsigned short s_list[16 * kListStride + 2];
+  const int tile = ordered_tile(nullptr, (int)blockIdx.x, num_tiles);
+  if (tile >= num_tiles) return;
+  const int c0 = (int)blockIdx.y * K;  // (more than one chunk: K = 16)
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, row = lane >> 4, j = lane & 15;
+  if (tid == 0) {
+    s_r0[kBatch] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    s_r1[kBatch] = sentinel_r1();
+    s_tile_top = 0;
+  }
+  const int tile_x = tile % ntx, tile_y = tile / ntx;
+  const int px = tile_x * 16 + (wave & 1) * 8 + (row & 1) * 4 + (j & 3);
+  const int py = tile_y * 16 + (wave >> 1) * 8 + (row >> 1) * 4 + (j >> 2);
+  const bool inside = px < width && py < height;
+  const float fpx = (float)px, fpy = (float)py;
+  const float tx0 = (float)(tile_x * 16), ty0 = (float)(tile_y * 16);
+  const char *r0b = reinterpret_cast<const char *>(s_r0), *r1b = reinterpret_cast<const char *>(s_r1);
+  const int start = ranges[tile], total = ranges[tile + 1] - start;
+  const int n = inside ? min(n_px[py * width + px], total) : 0;
+  float m[K];  // the pixel's map values of this chunk (an outside pixel: zeros, and T = 0 below)
+#pragma unroll
+  for (int c = 0; c < K; ++c) m[c] = 0.0f;
+  if (inside) {
+    const float *mp = map + (size_t)(py * width + px) * (size_t)channels + c0;
+    if (vec) {
+#pragma unroll
+      for (int q = 0; q < K / 4; ++q)
+        if (c0 + 4 * q < channels) {
+          const float4 v = reinterpret_cast<const float4 *>(mp)[q];
+          m[4 * q] = v.x; m[4 * q + 1] = v.y; m[4 * q + 2] = v.z; m[4 * q + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+      for (int c = 0; c < K; ++c)
+        if (c0 + c < channels) m[c] = mp[c];
+    }
+  }
+  float mk[K / 2], ms[K / 2];  // ... as the row reduction's first stage takes them
+  transpose_operands<K>(m, j, mk, ms);
+  const int row_top = row_max_int(n);
+  const int top0 = __builtin_amdgcn_readlane(row_top, 0), top1 = __builtin_amdgcn_readlane(row_top, 16);
+  const int top2 = __builtin_amdgcn_readlane(row_top, 32), top3 = __builtin_amdgcn_readlane(row_top, 48);
+  __syncthreads();
+  if (lane == 0) atomicMax(&s_tile_top, max(max(top0, top1), max(top2, top3)));
+  __syncthreads();
+  const int top = s_tile_top;
+  const RawSplats none = {nullptr, nullptr, nullptr, nullptr};
+  unsigned short *lists = s_list + wave * 4 * kListStride;
+  const unsigned short *my_list = lists + row * kListStride;
+  float T = inside ? 1.0f : 0.0f;
+  for (int base = 0; base < top; base += kBatch) {
+    const int count = min(kBatch, top - base);
+    __syncthreads();  // the flush of the batch before has read the accumulators
+    if (tid < count) {
+      const int g = sorted[start + base + tid];
+      SplatRec s = load_record<true>(g, recs, none);
+      const unsigned int hits = block_hits(s, tx0, ty0);
+      stage_record(s);
+      s_r0[tid] = s.r0;
+      s_r1[tid] = make_float4(s.r1.x, s.r1.y, s.r1.y > kLog2AlphaMax ? kLog2AlphaMax : s.r1.y, __uint_as_float(hits));
+      s_gid[tid] = g;
+    }
+    for (int e = tid; e < count * K; e += 256) s_acc[e] = 0.0;
+    __syncthreads();
+    const RowCounts rc = build_row_lists<kListStride>(s_r1, lists, count, wave, lane, top0 - base, top1 - base, top2 - base,
+                                                      top3 - base, 1);
+    const int trips = max(max(rc.c0, rc.c1), max(rc.c2, rc.c3));
+    for (int i = 0; i < trips; ++i) {
+      const int off = my_list[i];  // a row past the end of its list reads the sentinel record: alpha 0
+      const float4 a = *reinterpret_cast<const float4 *>(r0b + off), b = *reinterpret_cast<const float4 *>(r1b + off);
+      float al = staged_alpha_capped(a.z, a.w, b.x, b.y, b.z, a.x - fpx, a.y - fpy);
+      const bool on = al > kAlphaMin && base + (off >> 4) < n;
+      al = on ? al : 0.0f;
+      const float w = al * T;
+      T = __builtin_fmaf(-al, T, T);
+      const float tot = row_transpose_sum<K>(w, mk, ms, j);  // lane j < K: channel j's sum of w map over the row's 16 pixels
+      // every lane that holds a total adds it, zero or not (the sentinel slot's accumulators are never read)
+      if (j < K)
+        __hip_atomic_fetch_add((__attribute__((address_space(3))) double *)(&s_acc[(off >> 4) * K + j]), (double)tot,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __syncthreads();
+    for (int e = tid; e < count * K; e += 256) {  // (slot, channel) = (e / K, e % K)
+      const float tot = (float)s_acc[e];
+      const int c = c0 + (e & (K - 1));
+      if (tot != 0.0f && c < channels) atomicAdd(lifted + (size_t)c2g[s_gid[e / K]] * (size_t)channels + c, tot);
+    }
+  }
+}
+
 // host-side launchers called from gs_fused.hip (gs_launch.h) ------------------------------
 // One launch of `kernel`, its arguments converted to its parameter types.  With both events it is a timed launch (the
 // context's per-stage timing): the events take the begin and end timestamps of THIS dispatch from its completion signal.
@@ -2042,6 +2314,40 @@ int launch_contributions(const float4 *recs, const int *sorted, const int *range
   contributions_kernel<<<dim3(tile_grid(num_tiles)), dim3(256), 0, st>>>(recs, sorted, ranges, n_px, c2g, width, height, ntx,
                                                                          num_tiles, weight_sum,
                                                                          reinterpret_cast<unsigned int *>(weight_max), pixels);
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+// the chunk width of a launch: the smallest of 4 / 8 / 16 that holds all channels, 16 beyond (gridDim.y chunks then);
+// 16-byte accesses to the caller's [.., C] array when C is a multiple of 4 and the array starts on 16 bytes
+template <class F>
+static void with_chunk_width(int channels, F &&f) {
+  if (channels <= 4) f(std::integral_constant<int, 4>{});
+  else if (channels <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+static int rows_vectorised(const void *p, int channels) { return (channels & 3) == 0 && ((size_t)p & 15) == 0 ? 1 : 0; }
+
+int launch_features_fwd(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
+                        int width, int height, int channels, const float *features, float *out, hipStream_t st) {
+  const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
+  with_chunk_width(channels, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    features_fwd_kernel<K><<<dim3(tile_grid(num_tiles), (channels + K - 1) / K), dim3(256), 0, st>>>(
+        recs, sorted, ranges, n_px, c2g, width, height, ntx, num_tiles, channels, features, out, rows_vectorised(out, channels));
+  });
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int launch_features_lift(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
+                         int width, int height, int channels, const float *map, float *lifted, hipStream_t st) {
+  const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
+  with_chunk_width(channels, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    features_lift_kernel<K><<<dim3(tile_grid(num_tiles), (channels + K - 1) / K), dim3(256), 0, st>>>(
+        recs, sorted, ranges, n_px, c2g, width, height, ntx, num_tiles, channels, map, lifted, rows_vectorised(map, channels));
+  });
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;
 }

@@ -124,7 +124,7 @@ class RasterContext:
         h = ctypes.c_void_p()
         check(self._lib.gsplat_context_create(ctypes.byref(h), int(max_gaussians), int(max_width), int(max_height)))
         self._h = h
-        self._last = None
+        self._last = self._last_size = None
         self._depth = self._depth_inverse = self._depth_moment = False
         self._filter3d = self._filter3d_fwd = None
         self.max_gaussians, self.max_width, self.max_height = int(max_gaussians), int(max_width), int(max_height)
@@ -237,6 +237,60 @@ class RasterContext:
         check(self._lib.gsplat_context_accumulate_contributions(self._h, int(n), _ptr(weight_sum), _ptr(weight_max),
                                                                 _ptr(pixels), st))
 
+    @staticmethod
+    def _dense(name, t, dims):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                or t.dim() != dims):
+            raise ValueError("%s must be a contiguous %s float32 device tensor" % (name, "[N,C]" if dims == 2 else "[H,W,C]"))
+        return t
+
+    def render_features(self, features, out=None):
+        """The caller's per-gaussian channels through the last forward (gsplat_context_render_features): features [N,C]
+        float32 in global gaussian order -> the [H,W,C] map out[p, c] = sum over the gaussians the forward composited
+        at p of alpha * T * features[j, c], in the forward's own weights (no background term: fwd["T"] is what is left
+        of the pixel).  `out`: an [H,W,C] tensor to write into, else a new one; returned.  1 <= C <= 512.  Every pixel is
+        summed in list order without atomics: the map is bit-reproducible, and with the forward's colours it is the
+        forward's image at background 0.  Works after any forward (render-only included), before or after its backward.
+        The geometry is frozen: nothing here is differentiated with respect to opacity, conic or position; the gradient
+        of a loss on the map with respect to `features` is lift_features of the loss's gradient map."""
+        self._dense("features", features, 2)
+        N, C = int(features.shape[0]), int(features.shape[1])
+        if not 1 <= C <= 512:
+            raise ValueError("features must have 1 .. 512 channels, not %d" % C)
+        H, W = self._feature_map_shape()
+        if out is None:
+            out = torch.empty(H, W, C, dtype=torch.float32, device=features.device)
+        elif tuple(self._dense("out", out, 3).shape) != (H, W, C):
+            raise ValueError("out must be [%d,%d,%d], not %s" % (H, W, C, list(out.shape)))
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self._lib.gsplat_context_render_features(self._h, N, C, _ptr(features), _ptr(out), st))
+        return out
+
+    def lift_features(self, map, out):
+        """render_features' adjoint (gsplat_context_lift_features): map [H,W,C] float32 of the last forward's size ->
+        out[j, c] += sum over the pixels that composited gaussian j of alpha * T * map[p, c]; out is [N,C] float32 in
+        global gaussian order, accumulated INTO and returned.  Rows of culled gaussians, and of gaussians no pixel
+        composited, are untouched, so one array gathers a camera set: clear it once, call after each view's forward.
+        With a map of ones this is accumulate_contributions' weight_sum; the quotient of the two is the weighted mean
+        of what a gaussian's pixels said (label lifting).  The sums are float atomics: order-dependent in their last
+        bits."""
+        self._dense("map", map, 3)
+        self._dense("out", out, 2)
+        N, C = int(out.shape[0]), int(out.shape[1])
+        if not 1 <= C <= 512:
+            raise ValueError("out must have 1 .. 512 channels, not %d" % C)
+        H, W = self._feature_map_shape()
+        if tuple(map.shape) != (H, W, C):
+            raise ValueError("map must be [%d,%d,%d], not %s" % (H, W, C, list(map.shape)))
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self._lib.gsplat_context_lift_features(self._h, N, C, _ptr(map), _ptr(out), st))
+        return out
+
+    def _feature_map_shape(self):
+        if self._last_size is None:  # (the library's own answer to a call before the first forward)
+            raise _lib.GsplatError(-3, "no forward pass recorded in this context")
+        return self._last_size
+
     def set_preprocess_split(self, mode):
         """How the per-gaussian forward is launched: 0 (default) the single fused kernel, 1 SH colour then geometry on the
         caller's stream, 2 the two side by side on two streams (gsplat_context_set_preprocess_split); every output is
@@ -330,6 +384,7 @@ class RasterContext:
                 out._specs["depth2"] = (qp.value, (H, W), "<f4")
         out._derived["alpha"] = _alpha  # the opacity map: 1 - the final transmittance
         self._last = (g.num_gaussians, M, l_max)
+        self._last_size = (H, W)
         return out._all() if _EAGER_VIEWS else out
 
     def alloc_gradients(self, M, l_max, intermediates=False, device="cuda", factored_sh=False):

@@ -563,6 +563,61 @@ class Trainer:
             ctx.set_render_only(False)
         return out
 
+    def render_features(self, cam, features):
+        """The [H,W,C] map of the caller's per-gaussian channels `features` ([N,C] float32 device tensor, one row per
+        gaussian in the current order) from `cam`: a render-only forward at background 0 in the mode the run trains in,
+        then RasterContext.render_features on it (sum of alpha * T * features over the gaussians a pixel composites;
+        no background term).  The geometry is frozen: the map has no gradient with respect to the gaussians.
+
+        `features` is the caller's tensor, not a column of the trainer's row table: whatever changes the set or the
+        order of the gaussians (densification, pruning, relocation, the Morton re-order) invalidates it."""
+        if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] != self.num_gaussians:
+            raise ValueError("features must be an [N,C] tensor with one row per gaussian (N = %d)" % self.num_gaussians)
+        ctx = self._context_for(self.num_gaussians)
+        ctx.set_render_only(True)
+        try:
+            ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
+            return ctx.render_features(features)
+        finally:
+            ctx.set_render_only(False)
+
+    def lift_maps(self, views_and_maps, normalize=True):
+        """[N,C] float32: the maps of `views_and_maps` ((camera, map [H,W,C] float32 device tensor) pairs) lifted onto
+        the gaussians that produced their pixels (RasterContext.lift_features on a render-only forward at background 0
+        of every view, in the mode the run trains in), summed over the views.  normalize: divided by the gaussian's
+        summed blend weight over the same views (accumulate_contributions' weight_sum) -- the weighted mean of what
+        its pixels said: label lifting.  Rows no pixel composited stay 0; a view in which nothing is visible
+        contributes nothing.  The rows follow the current order of the gaussians (see render_features)."""
+        views_and_maps = list(views_and_maps)
+        if not views_and_maps:
+            raise ValueError("lift_maps needs at least one (camera, map) pair")
+        for _, m in views_and_maps:
+            if not isinstance(m, torch.Tensor) or m.dim() != 3 or m.shape[2] != views_and_maps[0][1].shape[2]:
+                raise ValueError("every map must be an [H,W,C] tensor with the same C")
+        n, dev = self.num_gaussians, self.params["xyz"].device
+        lifted = torch.zeros(n, int(views_and_maps[0][1].shape[2]), dtype=torch.float32, device=dev)
+        weight = torch.zeros(n, dtype=torch.float32, device=dev)
+        if n == 0:
+            return lifted
+        ctx = self._context_for(n)
+        ctx.set_render_only(True)
+        try:
+            for cam, m in views_and_maps:
+                try:
+                    ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
+                except Exception as e:  # no gaussian in view
+                    if getattr(e, "code", None) != -5:
+                        raise
+                    continue
+                ctx.lift_features(m, lifted)
+                if normalize:
+                    ctx.accumulate_contributions(weight_sum=weight)
+        finally:
+            ctx.set_render_only(False)
+        if normalize:
+            lifted = torch.where(weight[:, None] > 0, lifted / weight[:, None].clamp_min(1e-38), torch.zeros_like(lifted))
+        return lifted
+
     def prune_by_contribution(self, threshold=None, views=None, scores=None):
         """Remove the gaussians that no pixel of `views` composites (pixels == 0) or whose largest blend weight over them
         is below `threshold` (default: the config's prune_contribution_threshold; 0 removes only the never-composited

@@ -659,6 +659,30 @@ int gsplat_backward_pass_camera(gsplat_context *ctx, const gsplat_gaussians *gau
 int gsplat_context_accumulate_contributions(gsplat_context *ctx, int num_gaussians, float *weight_sum,
                                             float *weight_max, int *pixels, void *stream);
 
+/* Feature maps of the last completed forward (no ABI bump: new entry points only): the caller's own per-gaussian
+ * channels carried through the renderer, and pixel maps lifted back onto the gaussians.  With w_jp the blend weight of
+ * gsplat_context_accumulate_contributions above (same entries, same alpha, same T):
+ *   gsplat_context_render_features   out[p, c]     = sum_j w_jp features[j, c]        features [N,C], out [H,W,C]
+ *   gsplat_context_lift_features     lifted[j, c] += sum_p w_jp map[p, c]             map [H,W,C], lifted [N,C]
+ * each the other's adjoint: <render(f), g> = <f, lift(g)> (lifted cleared first).  features and lifted are in GLOBAL
+ * gaussian order, 1 <= channels <= 512, all four are dense device arrays.  There is no background term: the map is what
+ * the gaussians contribute, the forward's weight_per_pixel says how much of a pixel is left.  render_features writes every
+ * pixel of out; a pixel's sum runs in list order without atomics, so the map is bit-reproducible -- in every run, under
+ * either binning route, channel by channel at every `channels`, and with the forward's own colours it is the forward's
+ * image at background 0.  lift_features ACCUMULATES into lifted (rows of culled gaussians and of gaussians no pixel
+ * composited are not touched: clear once, call after each view's forward to gather a camera set) with float atomics: not
+ * bit-reproducible in the last bits, as weight_sum.  With a map of ones and channels = 1 it is weight_sum.
+ * The geometry is FROZEN: neither call differentiates a feature loss with respect to opacity, conic or position -- the
+ * gradient of a loss on `out` with respect to `features` is lift_features of the loss's gradient map, and that is all.
+ * Calling conditions, checks (all before any launch; a refused call leaves the caller's arrays as they were) and `stream`
+ * as for gsplat_context_accumulate_contributions; a backward after them is unaffected.  A tile list longer than 1488
+ * entries is walked whole by one workgroup (per chunk of 16 channels). */
+int gsplat_context_render_features(gsplat_context *ctx, int num_gaussians, int channels,
+                                   const float *features /* [N,C], global order */, float *out /* [H,W,C] */,
+                                   void *stream);
+int gsplat_context_lift_features(gsplat_context *ctx, int num_gaussians, int channels, const float *map /* [H,W,C] */,
+                                 float *lifted /* [N,C], global order, += */, void *stream);
+
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
  * tiles, stable radix sorts on (depth bits, tile).  1 / 2 force one route.  Both produce identical lists. */
