@@ -232,6 +232,7 @@ SIGNATURES = {
     "gsplat_context_accumulate_contributions": (_I, [_P, _I, _P, _P, _P, _P]),
     "gsplat_context_render_features": (_I, [_P, _I, _I, _P, _P, _P]),
     "gsplat_context_lift_features": (_I, [_P, _I, _I, _P, _P, _P]),
+    "gsplat_context_features_backward": (_I, [_P, _I, _I, _P, _P, _P]),
     "gsplat_context_set_absgrad": (_I, [_P, _I]),
     "gsplat_context_set_compact_lists": (_I, [_P, _I]),
     "gsplat_context_absgrad_uv": (_I, [_P, _P, _P]),

@@ -247,6 +247,25 @@ int gsplat_context_lift_features(gsplat_context *c, int num_gaussians, int chann
                                   c->c2g.as<int>(), c->width, c->height, channels, map, lifted, (hipStream_t)stream);
 }
 
+int gsplat_context_features_backward(gsplat_context *c, int num_gaussians, int channels, const float *features,
+                                     const float *grad_map, void *stream) {
+  // (every check before the launch: a refused call leaves the gradient rows and the caller's arrays as they were; every
+  // refusal of this entry point is GSPLAT_ERR_INVALID_ARG, a null or non-device pointer included)
+  GS_REQUIRE(c != nullptr, "null context");
+  GS_REQUIRE(c->lists_ready, "no forward pass recorded in this context");
+  GS_REQUIRE(c->have_forward && c->rows_ready,
+             "gsplat_backward_render has not run for this forward pass: the feature term is added to its gradient rows");
+  GS_REQUIRE(num_gaussians == c->N, "does not match the recorded forward");
+  GS_REQUIRE(channels >= 1 && channels <= 512, "channels must be 1 .. 512");
+  GS_REQUIRE(features != nullptr && gs::check_device_ptr(features, "features", __func__) == GSPLAT_OK,
+             "features must be a device pointer");
+  GS_REQUIRE(grad_map != nullptr && gs::check_device_ptr(grad_map, "grad_map", __func__) == GSPLAT_OK,
+             "grad_map must be a device pointer");
+  return gs::launch_features_bwd(c->recs.as<float4>(), c->sorted.as<int>(), c->ranges.as<int>(), c->n_px.as<int>(),
+                                 c->T_px.as<float>(), c->c2g.as<int>(), c->width, c->height, channels, features, grad_map,
+                                 c->grad_rows.as<float>(), (hipStream_t)stream);
+}
+
 int gsplat_context_depth_map(gsplat_context *c, const float **depth) {
   GS_REQUIRE(c && depth, "null argument");
   *depth = nullptr;

@@ -59,6 +59,11 @@ int launch_features_fwd(const float4 *recs, const int *sorted, const int *ranges
                         int width, int height, int channels, const float *features, float *out, hipStream_t st);
 int launch_features_lift(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
                          int width, int height, int channels, const float *map, float *lifted, hipStream_t st);
+// the feature map's gradient with respect to the geometry (features_bwd_kernel): features [N,C] in global order and
+// grad_map [H,W,C] -> columns 3..8 (opacity logit, conic, uv) of the gradient rows [M,16], added to what they hold
+int launch_features_bwd(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const float *T_px,
+                        const int *c2g, int width, int height, int channels, const float *features, const float *grad_map,
+                        float *rows, hipStream_t st);
 int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
 bool tile_order_supported(int num_tiles);
 

@@ -449,6 +449,34 @@ __device__ __host__ __forceinline__ int row_moments9r_index(int lane) {
   return j < 3 ? j : j == 4 ? 3 : j == 5 ? 4 : j == 6 ? 6 : j == 8 ? 5 : j == 9 ? 7 : j == 11 ? 8 : -1;
 }
 
+// row_moments9r without the colour sums (features_bwd_kernel: the colours are the caller's): the six moments of gp only,
+// in the lanes row_moments9r_index gives them (sums 3..8).  The same instructions with the same spacing; the register of
+// the colour totals starts as zero instead of the four aT products, which frees the four colour weights and aT itself
+// (lanes 0..2 of the result hold zeros and are not added).  `addr` <- off * kMul + acc_lane as there.
+template <int kMul>
+__device__ __forceinline__ float row_moments6r(float gp, const RowsWeights &w, unsigned int off, unsigned int acc_lane,
+                                               unsigned int &addr) {
+  float A, B, Q;
+  asm volatile(
+      // two plain instructions first: the wait states between the instruction that wrote gp and its first DPP read
+      "v_mul_f32 %[B], %[gp], %[b0]\n\t"
+      "v_mov_b32 %[A], 0\n\t"
+      "v_fmac_f32_dpp %[B], %[gp], %[b1] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp %[B], %[gp], %[b2] quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+      "v_fmac_f32_dpp %[B], %[gp], %[b3] quad_perm:[3,2,1,0] row_mask:0xf bank_mask:0xf\n\t"
+      "v_mul_f32 %[Q], %[B], %[wq]\n\t"
+      "v_add_f32_dpp %[A], %[A], %[A] row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_add_f32_dpp %[A], %[B], %[B] row_shr:4 row_mask:0xf bank_mask:0xa bound_ctrl:0\n\t"
+      "v_add_f32_dpp %[Q], %[Q], %[Q] row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_mad_u32_u24 %[addr], %[off], %[mul], %[acc]\n\t"
+      "v_add_f32_dpp %[A], %[A], %[A] row_shl:8 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_add_f32_dpp %[A], %[Q], %[Q] row_shr:8 row_mask:0xf bank_mask:0xc bound_ctrl:0\n\t"
+      : [A] "=&v"(A), [B] "=&v"(B), [Q] "=&v"(Q), [addr] "=&v"(addr)
+      : [gp] "v"(gp), [b0] "v"(w.b[0]), [b1] "v"(w.b[1]), [b2] "v"(w.b[2]), [b3] "v"(w.b[3]), [wq] "v"(w.q), [off] "v"(off),
+        [acc] "v"(acc_lane), [mul] "n"(kMul));
+  return A;
+}
+
 // ---- absgrad mode (gsplat_context_set_absgrad): the same sums plus the row totals of two per-pixel ABSOLUTE values,
 //   U = |gp| |pu|,  V = |gp| |pv|,   (pu, pv) = (2 a2 dx + b2 dy, 2 c2 dy + b2 dx)  in the staged conic (stage_record),
 // i.e. |d/du| and |d/dv| of this pixel's share up to the per-gaussian factor -kConicOff x (0.5 W | 0.5 H) the flush

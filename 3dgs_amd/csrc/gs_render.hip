@@ -2222,6 +2222,205 @@ __global__ __launch_bounds__(256) void features_lift_kernel(const float4 *__rest
   }
 }
 
+// features_bwd_kernel: the feature map's gradient with respect to the GEOMETRY (gsplat_context_features_backward).  With
+// G[p, c] = dL/d out[p, c] and d_i(p) = sum_c G[p, c] f[g_i, c], the map out[p, c] = sum_i w_ip f[g_i, c] is the
+// forward's image with colours f, pixel gradient G and background 0, so d/d alpha_i(p) = T_i (d_i - s_i), s_i = the
+// "colour behind" entry i dotted with G -- render_bwd_kernel's ga with a C-vector per pixel.  The expression is linear in
+// (f, G) over channels: every chunk of K channels (gridDim.y, as above) walks the list with its own s and adds its own
+// part.  The walk is render_bwd_kernel's, back to front from T_px (T rebuilt by the same rcp of 1 - the forward's capped
+// alpha, gp = og ga with the uncapped og: the 0.99 cap is differentiated as if absent), on what features_lift_kernel
+// reads: the full sorted / ranges / n_px and block_hits recomputed, no compact lists and no segments (a list longer
+// than kSegSplitMin is walked whole), in batches of GS_BWD_BATCH (T comes from T_px, so the batches need not be the
+// forward's).  Per batch the records and the chunk's slice of the feature rows are staged with features_fwd_kernel's
+// gather; per trip a lane forms d_i as a K-term FMA chain over the staged row (K/4 broadcast reads), runs
+// t = d_i - s, s = fma(alpha, t, s), and the six moments of gp about the tile centre are reduced over the row by
+// row_moments6r (row_moments9r without the colour sums: lanes 0..2 of the totals are not added) and added with one
+// ds_add_f64 per wave and trip into [slot][6] doubles.  Behind the batch one thread per gaussian forms row columns 3..8
+// exactly as render_bwd_kernel's flush does (same gate: nothing for sigmoid(opacity) == 1 or gp zero on the whole tile)
+// and 16 lanes per gaussian add the non-zero ones to the gradient rows with float atomics (NaN goes out).  Columns 0..2
+// (the colours are the caller's: lift_features), 9 and the absgrad columns 10, 11 are never written.
+// waves per SIMD the kernel is compiled for: five -- 84 / 88 / 96 VGPRs at K = 4 / 8 / 16, no scratch.  Occupancy is
+// what it is bound by at K = 16: with row_moments9r on zero colour weights it held 98 VGPRs, four waves, and took
+// 0.666 ms at C = 16 on config 3; held to five waves with two spilled registers 0.591 ms; asked for six every K spills
+#ifndef GS_FEAT_BWD_WAVES
+#define GS_FEAT_BWD_WAVES 5
+#endif
+template <int K>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FEAT_BWD_WAVES, 8))) void features_bwd_kernel(const float4 *__restrict__ recs, const int *__restrict__ sorted,
+                                                           const int *__restrict__ ranges, const int *__restrict__ n_px,
+                                                           const float *__restrict__ T_px, const int *__restrict__ c2g,
+                                                           int width, int height, int ntx, int num_tiles, int channels,
+                                                           const float *__restrict__ features,
+                                                           const float *__restrict__ grad_map, float *__restrict__ rows,
+                                                           int vec) {
+  static_assert(K == 4 || K == 8 || K == 16, "chunk widths");
+  constexpr int kB = GS_BWD_BATCH, kQ = K / 4, kAcc = 6;
+  // r0 = (u, v, a2, b2), r1 = (c2, log2 opa, opa, block-hit bits); [kB]: the sentinel
+  __shared__ float4 s_r0[kB + 1], s_r1[kB + 1];
+  __shared__ float4 s_feat[(kB + 1) * kQ];    // [slot][K]; the sentinel's row is zeros
+  __shared__ double s_acc[(kB + 1) * kAcc];   // [slot][S1, Sx, Sy, Sxx, Sxy, Syy]; doubles: see features_lift_kernel
+  __shared__ int s_id[kB];
+  // the row lists; dead once the batch's trips are done, and the flush parks its six values per gaussian on top of them
+  __shared__ __attribute__((aligned(16))) unsigned short s_list[16 * kB + 2];
+  static_assert(kB * kAcc * 4 <= 16 * kB * 2, "the flush values fit on the row lists");
+  __shared__ int s_top;
+  const int tile = ordered_tile(nullptr, (int)blockIdx.x, num_tiles);
+  if (tile >= num_tiles) return;
+  const int c0 = (int)blockIdx.y * K;  // (more than one chunk: K = 16)
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, row = lane >> 4, j = lane & 15;
+  if (tid == 0) {
+    s_r0[kB] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    s_r1[kB] = sentinel_r1();
+    s_top = 0;
+  }
+  if (tid < kQ) s_feat[kB * kQ + tid] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  const int tile_x = tile % ntx, tile_y = tile / ntx;
+  const int px = tile_x * 16 + (wave & 1) * 8 + (row & 1) * 4 + (j & 3);
+  const int py = tile_y * 16 + (wave >> 1) * 8 + (row >> 1) * 4 + (j >> 2);
+  const bool inside = px < width && py < height;
+  const float fpx = (float)px, fpy = (float)py;
+  const float tx0 = (float)(tile_x * 16), ty0 = (float)(tile_y * 16);
+  const char *r0b = reinterpret_cast<const char *>(s_r0), *r1b = reinterpret_cast<const char *>(s_r1);
+  const char *fb = reinterpret_cast<const char *>(s_feat);
+  float *s_feat_f = reinterpret_cast<float *>(s_feat);
+  float *s_res = reinterpret_cast<float *>(s_list);
+  const int start = ranges[tile], total = ranges[tile + 1] - start;
+  int n = 0;
+  float T = 0.0f;
+  float G[K];  // the pixel's gradient-map values of this chunk (an outside pixel: zeros, and it walks nothing)
+#pragma unroll
+  for (int c = 0; c < K; ++c) G[c] = 0.0f;
+  if (inside) {
+    const int pid = py * width + px;
+    n = min(n_px[pid], total);
+    T = T_px[pid];
+    const float *gp = grad_map + (size_t)pid * (size_t)channels + c0;
+    if (vec) {
+#pragma unroll
+      for (int q = 0; q < kQ; ++q)
+        if (c0 + 4 * q < channels) {
+          const float4 v = reinterpret_cast<const float4 *>(gp)[q];
+          G[4 * q] = v.x; G[4 * q + 1] = v.y; G[4 * q + 2] = v.z; G[4 * q + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+      for (int c = 0; c < K; ++c)
+        if (c0 + c < channels) G[c] = gp[c];
+    }
+  }
+  const int row_top = row_max_int(n);
+  const int top0 = __builtin_amdgcn_readlane(row_top, 0), top1 = __builtin_amdgcn_readlane(row_top, 16);
+  const int top2 = __builtin_amdgcn_readlane(row_top, 32), top3 = __builtin_amdgcn_readlane(row_top, 48);
+  const int wave_top = max(max(top0, top1), max(top2, top3));
+  __syncthreads();
+  if (lane == 0) atomicMax(&s_top, wave_top);
+  __syncthreads();
+  const int top = s_top;
+  if (top <= 0) return;
+  const RawSplats none = {nullptr, nullptr, nullptr, nullptr};
+  // where this lane's share of the row totals goes: row_moments9r's sums 3..8 are accumulators 0..5
+  const int red_idx = row_moments9r_index(lane) - 3;
+  const bool red_lane = red_idx >= 0;
+  const unsigned int acc_lane =
+      (unsigned int)(size_t)(__attribute__((address_space(3))) char *)reinterpret_cast<char *>(s_acc) + (unsigned int)(max(red_idx, 0) * 8);
+  const float alpha_cap = __builtin_amdgcn_exp2f(kLog2AlphaMax);
+  // the lane constants of the six moments: pixel position relative to the tile centre; no colour sums (weights 0)
+  const RowsWeights rw = make_rows_weights(lane, fpx - (tx0 + 7.5f), fpy - (ty0 + 7.5f), 0.0f, 0.0f, 0.0f);
+  unsigned short *lists = s_list + wave * 4 * kB;
+  const unsigned short *my_list = lists + row * kB;
+  float s = 0.0f;  // G . (features behind the current entry): background 0
+  for (int base = ((top - 1) / kB) * kB; base >= 0; base -= kB) {
+    const int count = min(kB, top - base);
+    __syncthreads();  // the flush of the batch before has read the parked values and the ids
+    if (tid < count) {
+      const int g = sorted[start + base + tid];
+      SplatRec r = load_record<true>(g, recs, none);
+      const unsigned int hits = block_hits(r, tx0, ty0);
+      stage_record(r);
+      s_r0[tid] = r.r0;
+      s_r1[tid] = make_float4(r.r1.x, r.r1.y, r.r1.z, __uint_as_float(hits));
+      s_id[tid] = g;
+    }
+    for (int e = tid; e < count * K; e += 256) {  // (slot, channel) = (e / K, e % K)
+      const int c = c0 + (e & (K - 1));
+      const size_t gi = (size_t)c2g[sorted[start + base + e / K]];
+      s_feat_f[e] = c < channels ? features[gi * (size_t)channels + c] : 0.0f;
+    }
+    for (int e = tid; e < count * kAcc; e += 256) s_acc[e] = 0.0;
+    __syncthreads();
+    if (base < wave_top) {
+      const RowCounts rc = build_row_lists<kB>(s_r1, lists, count, wave, lane, top0 - base, top1 - base, top2 - base,
+                                               top3 - base, 1);
+      const int trips = max(max(rc.c0, rc.c1), max(rc.c2, rc.c3));
+      for (int i = trips - 1; i >= 0; --i) {
+        const int off = my_list[i];  // a row past the end of its list reads the sentinel record: alpha 0, features 0
+        const float4 a = *reinterpret_cast<const float4 *>(r0b + off), b = *reinterpret_cast<const float4 *>(r1b + off);
+        // the forward's alpha bit for bit: staged_alpha is its exponent chain, the cap is taken below
+        float og = staged_alpha(a.z, a.w, b.x, b.y, a.x - fpx, a.y - fpy);
+        // (n is 0 for pixels outside the image; "not below" lets a NaN pass, as in render_bwd_kernel)
+        const bool valid = !(og < kAlphaMin) && base + (off >> 4) < n;
+        if (__ballot(valid) == 0ull) continue;
+        og = valid ? og : 0.0f;
+        float alpha;  // v_exp_f32(kLog2AlphaMax): the cap the forward composed with (see render_bwd_kernel)
+        asm("v_min_f32 %0, %2, %1" : "=v"(alpha) : "v"(og), "v"(alpha_cap));
+        T *= __builtin_amdgcn_rcpf(1.0f - alpha);  // transmittance in front of this entry
+        const float4 *f = reinterpret_cast<const float4 *>(fb + off * kQ);
+        float d = 0.0f;  // d_i = sum_c G[c] f[c], one chain in channel order
+#pragma unroll
+        for (int q = 0; q < kQ; ++q) {
+          const float4 v = f[q];
+          d = q == 0 ? v.x * G[0] : __builtin_fmaf(v.x, G[4 * q], d);
+          d = __builtin_fmaf(v.y, G[4 * q + 1], d);
+          d = __builtin_fmaf(v.z, G[4 * q + 2], d);
+          d = __builtin_fmaf(v.w, G[4 * q + 3], d);
+        }
+        const float t = d - s;
+        const float ga = t * T;  // d/d alpha
+        s = __builtin_fmaf(alpha, t, s);
+        const float gp = og * ga;  // d/d power
+        unsigned int acc_addr;
+        const float red = row_moments6r<3>(gp, rw, (unsigned int)off, acc_lane, acc_addr);
+        // every lane that holds a moment adds it, zero or not (rows past their list add zeros to the sentinel's slot)
+        if (red_lane)
+          __hip_atomic_fetch_add(reinterpret_cast<__attribute__((address_space(3))) double *>(acc_addr), (double)red,
+                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    __syncthreads();
+    // flush, step 1: one thread per gaussian turns its six moments into row columns 3..8 (render_bwd_kernel's flush)
+    if (tid < count) {
+      const double *acc = &s_acc[tid * kAcc];
+      const float4 a = s_r0[tid], b = s_r1[tid];
+      const float opa = b.z;
+      const double X = (double)(a.x - (tx0 + 7.5f)), Y = (double)(a.y - (ty0 + 7.5f));
+      const double S1 = acc[0], Sx = acc[1], Sy = acc[2];
+      const float sx = (float)(X * S1 - Sx), sy = (float)(Y * S1 - Sy);
+      const float sxx = (float)(X * (X * S1 - 2.0 * Sx) + acc[3]);
+      const float sxy = (float)(X * (Y * S1 - Sy) - Y * Sx + acc[4]);
+      const float syy = (float)(Y * (Y * S1 - 2.0 * Sy) + acc[5]);
+      const float ca = a.z * kConicDiag, cb = a.w * kConicOff, cc = b.x * kConicDiag;
+      const bool any_gp = (S1 != 0.0) | (Sx != 0.0) | (Sy != 0.0) | (acc[3] != 0.0) | (acc[4] != 0.0) | (acc[5] != 0.0);
+      const float keep = (opa == 1.0f || !any_gp) ? 0.0f : 1.0f;
+      float *res = &s_res[tid * kAcc];
+      res[0] = keep * ((float)S1 * (1.0f - opa));
+      res[1] = keep * (-0.5f * sxx);
+      res[2] = keep * -sxy;
+      res[3] = keep * (-0.5f * syy);
+      res[4] = keep * (-(ca * sx + cb * sy) * (0.5f * (float)width));
+      res[5] = keep * (-(cc * sy + cb * sx) * (0.5f * (float)height));
+    }
+    __syncthreads();
+    // step 2: 16 lanes per gaussian, six of them with a column each
+    if (j < kAcc) {
+      for (int slot = tid >> 4; slot < count; slot += 16) {
+        const float val = s_res[slot * kAcc + j];
+        if (!(val != 0.0f)) continue;  // zero (nothing to add) -- NaN still goes out
+        atomicAdd(&rows[(size_t)s_id[slot] * 16 + 3 + j], val);
+      }
+    }
+  }
+}
+
 // host-side launchers called from gs_fused.hip (gs_launch.h) ------------------------------
 // One launch of `kernel`, its arguments converted to its parameter types.  With both events it is a timed launch (the
 // context's per-stage timing): the events take the begin and end timestamps of THIS dispatch from its completion signal.
@@ -2347,6 +2546,20 @@ int launch_features_lift(const float4 *recs, const int *sorted, const int *range
     constexpr int K = decltype(k)::value;
     features_lift_kernel<K><<<dim3(tile_grid(num_tiles), (channels + K - 1) / K), dim3(256), 0, st>>>(
         recs, sorted, ranges, n_px, c2g, width, height, ntx, num_tiles, channels, map, lifted, rows_vectorised(map, channels));
+  });
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int launch_features_bwd(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const float *T_px,
+                        const int *c2g, int width, int height, int channels, const float *features, const float *grad_map,
+                        float *rows, hipStream_t st) {
+  const int ntx = (width + 15) / 16, nty = (height + 15) / 16, num_tiles = ntx * nty;
+  with_chunk_width(channels, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    features_bwd_kernel<K><<<dim3(tile_grid(num_tiles), (channels + K - 1) / K), dim3(256), 0, st>>>(
+        recs, sorted, ranges, n_px, T_px, c2g, width, height, ntx, num_tiles, channels, features, grad_map, rows,
+        rows_vectorised(grad_map, channels));
   });
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;

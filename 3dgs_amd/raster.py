@@ -251,8 +251,8 @@ class RasterContext:
         of the pixel).  `out`: an [H,W,C] tensor to write into, else a new one; returned.  1 <= C <= 512.  Every pixel is
         summed in list order without atomics: the map is bit-reproducible, and with the forward's colours it is the
         forward's image at background 0.  Works after any forward (render-only included), before or after its backward.
-        The geometry is frozen: nothing here is differentiated with respect to opacity, conic or position; the gradient
-        of a loss on the map with respect to `features` is lift_features of the loss's gradient map."""
+        The gradient of a loss on the map with respect to `features` is lift_features of the loss's gradient map; its
+        gradient with respect to opacity, conic and position is features_backward, behind backward_render."""
         self._dense("features", features, 2)
         N, C = int(features.shape[0]), int(features.shape[1])
         if not 1 <= C <= 512:
@@ -285,6 +285,26 @@ class RasterContext:
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         check(self._lib.gsplat_context_lift_features(self._h, N, C, _ptr(map), _ptr(out), st))
         return out
+
+    def features_backward(self, features, grad_map):
+        """The feature map's gradient with respect to the geometry (gsplat_context_features_backward): features [N,C]
+        float32 in global gaussian order, grad_map [H,W,C] = dL/d render_features(features).  Call it between
+        backward_render of the last forward and the per-gaussian call (backward_gaussians, _range, _split, _adam,
+        _camera): the loss's d/d opacity logit, conic and uv are ADDED to the gradient rows the compositing backward left,
+        so the per-gaussian call returns the gradient of the total down to xyz, opacity, scale and quaternion (for a
+        feature loss alone: backward_render with a zero grad_image).  Calling it twice adds twice.  The absgrad
+        statistic does not include the feature term, the signed grad_uv does.  The gradient with respect to `features`
+        is lift_features(grad_map)."""
+        self._dense("features", features, 2)
+        self._dense("grad_map", grad_map, 3)
+        N, C = int(features.shape[0]), int(features.shape[1])
+        if not 1 <= C <= 512:
+            raise ValueError("features must have 1 .. 512 channels, not %d" % C)
+        H, W = self._feature_map_shape()
+        if tuple(grad_map.shape) != (H, W, C):
+            raise ValueError("grad_map must be [%d,%d,%d], not %s" % (H, W, C, list(grad_map.shape)))
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self._lib.gsplat_context_features_backward(self._h, N, C, _ptr(features), _ptr(grad_map), st))
 
     def _feature_map_shape(self):
         if self._last_size is None:  # (the library's own answer to a call before the first forward)
@@ -415,11 +435,18 @@ class RasterContext:
         return gs
 
     def backward_pass(self, params, cam, grad_image, bg_color, l_max, grads, grad_depth=None, grad_alpha=None,
-                      grad_depth2=None):
+                      grad_depth2=None, feature_grads=None):
         """grads: dict from alloc_gradients (compacted order); every leaf gradient is overwritten.  grad_depth /
         grad_alpha ([H,W], depth mode, either may be None): dL/d of the forward's "depth" / "alpha" views, added to the
         image's gradient (gsplat_backward_pass_depth).  grad_depth2: dL/d of the "depth2" view (the moment option;
-        gsplat_backward_pass_depth2)."""
+        gsplat_backward_pass_depth2).  feature_grads: (features [N,C], grad_map [H,W,C]) of a loss on
+        render_features(features) -- its gradient with respect to the geometry is added (backward_render ->
+        features_backward -> backward_gaussians); None: the calls made are exactly the ones above."""
+        if feature_grads is not None:
+            features, grad_map = feature_grads
+            self.backward_render(grad_image, bg_color, grad_depth=grad_depth, grad_alpha=grad_alpha, grad_depth2=grad_depth2)
+            self.features_backward(features, grad_map)
+            return self.backward_gaussians(params, cam, l_max, grads)
         g, c = self._structs(params, cam, l_max)
         gs = self._grad_struct(grads)
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -437,13 +464,15 @@ class RasterContext:
         return grads
 
     def backward_pass_adam(self, params, cam, grad_image, bg_color, l_max, adam, grads=None, grad_depth=None,
-                           grad_alpha=None, grad_depth2=None):
+                           grad_alpha=None, grad_depth2=None, feature_grads=None):
         """backward_pass with the optimizer step inside (single-GPU training): the compositing backward, then ONE
         per-gaussian kernel that differentiates every visible gaussian and applies the masked Adam step to its rows of the
         parameters (`params`, in place), the moments and the densification statistics (gsplat_backward_gaussians_adam).
         adam: an _lib.AdamFused (AdamOptimizer.fused_state); grads: optional gradient arrays to fill as well;
-        grad_depth / grad_alpha / grad_depth2: as in backward_pass."""
+        grad_depth / grad_alpha / grad_depth2 / feature_grads: as in backward_pass."""
         self.backward_render(grad_image, bg_color, grad_depth=grad_depth, grad_alpha=grad_alpha, grad_depth2=grad_depth2)
+        if feature_grads is not None:
+            self.features_backward(*feature_grads)
         self.backward_gaussians_adam(params, cam, l_max, adam, grads)
 
     def backward_gaussians_adam(self, params, cam, l_max, adam, grads=None):

@@ -567,7 +567,8 @@ class Trainer:
         """The [H,W,C] map of the caller's per-gaussian channels `features` ([N,C] float32 device tensor, one row per
         gaussian in the current order) from `cam`: a render-only forward at background 0 in the mode the run trains in,
         then RasterContext.render_features on it (sum of alpha * T * features over the gaussians a pixel composites;
-        no background term).  The geometry is frozen: the map has no gradient with respect to the gaussians.
+        no background term).  Nothing is differentiated here: feature_gradients returns the gradients of a loss on the
+        map with respect to the gaussians and the features.
 
         `features` is the caller's tensor, not a column of the trainer's row table: whatever changes the set or the
         order of the gaussians (densification, pruning, relocation, the Morton re-order) invalidates it."""
@@ -580,6 +581,41 @@ class Trainer:
             return ctx.render_features(features)
         finally:
             ctx.set_render_only(False)
+
+    def feature_gradients(self, cam, features, grad_fn):
+        """The gradients of a loss on the feature map of `cam` with respect to the gaussians AND the features:
+        a training forward of the current state in the mode the run trains in, fmap = render_features(features),
+        grad_map = grad_fn(fmap) ([H,W,C] float32, dL/d fmap), then a compositing backward of a zero image gradient,
+        RasterContext.features_backward and the plain per-gaussian backward (the 3D filter's chain rule inside it, as in
+        train_step's unfused path).  Returns dict(xyz [N,3], opacity [N], scale [N,3], quaternion [N,4], features [N,C])
+        in the current order of the gaussians, zero for the gaussians the view culled; `features` is
+        lift_features(grad_map).  Nothing is trained: no iteration is counted, no moment or densification statistic is
+        touched -- a semantic or mask loss that should move the gaussians is stepped by the caller.  One rank only.
+
+        `features` is the caller's tensor (see render_features)."""
+        if self.world > 1:
+            raise ValueError("feature_gradients runs on one rank only")
+        if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] != self.num_gaussians:
+            raise ValueError("features must be an [N,C] tensor with one row per gaussian (N = %d)" % self.num_gaussians)
+        n, dev = self.num_gaussians, self.params["xyz"].device
+        ctx = self._context_for(n)
+        p = dict(self.params)
+        H, W = int(cam["height"]), int(cam["width"])
+        fwd = ctx.rasterize_image(p, cam, self.cfg, 0.0, self.l_max)
+        fmap = ctx.render_features(features)
+        grad_map = grad_fn(fmap)
+        m = int(fwd["num_culled"])
+        grads = ctx.alloc_gradients(m, self.l_max, device=dev)
+        ctx.backward_render(torch.zeros(H, W, 3, dtype=torch.float32, device=dev), 0.0)
+        ctx.features_backward(features, grad_map)
+        ctx.backward_gaussians(p, cam, self.l_max, grads)
+        c2g = fwd["compact_to_global"].long()
+        out = {}
+        for k, shape in (("xyz", (n, 3)), ("opacity", (n,)), ("scale", (n, 3)), ("quaternion", (n, 4))):
+            out[k] = torch.zeros(*shape, dtype=torch.float32, device=dev)
+            out[k][c2g] = grads[k].reshape((m,) + shape[1:])
+        out["features"] = ctx.lift_features(grad_map, torch.zeros_like(features))
+        return out
 
     def lift_maps(self, views_and_maps, normalize=True):
         """[N,C] float32: the maps of `views_and_maps` ((camera, map [H,W,C] float32 device tensor) pairs) lifted onto

@@ -672,8 +672,9 @@ int gsplat_context_accumulate_contributions(gsplat_context *ctx, int num_gaussia
  * image at background 0.  lift_features ACCUMULATES into lifted (rows of culled gaussians and of gaussians no pixel
  * composited are not touched: clear once, call after each view's forward to gather a camera set) with float atomics: not
  * bit-reproducible in the last bits, as weight_sum.  With a map of ones and channels = 1 it is weight_sum.
- * The geometry is FROZEN: neither call differentiates a feature loss with respect to opacity, conic or position -- the
- * gradient of a loss on `out` with respect to `features` is lift_features of the loss's gradient map, and that is all.
+ * Neither call differentiates anything: the gradient of a loss on `out` with respect to `features` is lift_features of
+ * the loss's gradient map, and its gradient with respect to opacity, conic and position is
+ * gsplat_context_features_backward below, which adds it to the gradient rows of the compositing backward.
  * Calling conditions, checks (all before any launch; a refused call leaves the caller's arrays as they were) and `stream`
  * as for gsplat_context_accumulate_contributions; a backward after them is unaffected.  A tile list longer than 1488
  * entries is walked whole by one workgroup (per chunk of 16 channels). */
@@ -682,6 +683,28 @@ int gsplat_context_render_features(gsplat_context *ctx, int num_gaussians, int c
                                    void *stream);
 int gsplat_context_lift_features(gsplat_context *ctx, int num_gaussians, int channels, const float *map /* [H,W,C] */,
                                  float *lifted /* [N,C], global order, += */, void *stream);
+
+/* The feature map's gradient with respect to the GEOMETRY (no ABI bump: a new entry point only).  With grad_map[p, c] =
+ * dL/d out[p, c] of a loss on gsplat_context_render_features' map, out is the forward's image with colours `features`,
+ * pixel gradient grad_map and background 0, for any number of channels: the call walks the recorded lists back to front
+ * as the compositing backward does and ADDS the loss's d/d opacity logit, d/d conic (3) and d/d uv (2) to the gradient
+ * rows gsplat_backward_render* left in the context (the 0.99 cap differentiated as if absent, nothing for a gaussian whose
+ * sigmoid(opacity) is 1 in float32, as there).  It sits between gsplat_backward_render* of the recorded forward and
+ * whichever per-gaussian call follows (gsplat_backward_gaussians, _range, _split, _adam, _camera), which then returns
+ * the gradient of the TOTAL loss down to xyz, opacity, scale and quaternion; the anti-aliased mode and the 3D filter
+ * need nothing new (their chain sits behind the rows).  Calling it twice adds twice; for a feature loss alone pass a
+ * zero grad_image to gsplat_backward_render.  The colour, depth and absgrad columns of the rows are not touched: the
+ * absgrad statistic (gsplat_context_set_absgrad) does NOT include the feature term, the signed grad_uv does.  The
+ * gradient with respect to `features` stays gsplat_context_lift_features(grad_map).  Float atomics: order-dependent in
+ * the last bits, as the rows are.
+ * Refused with GSPLAT_ERR_INVALID_ARG, before any launch and with the rows and the caller's arrays untouched: a null
+ * context, a null or non-device pointer, channels outside 1..512, num_gaussians not the forward's, no completed forward
+ * or its outputs detached (the conditions of gsplat_context_lift_features), and no compositing backward since the last
+ * forward.  `stream` must be the backward's stream or ordered behind it.  A tile list longer than 1488 entries is walked
+ * whole by one workgroup (per chunk of 16 channels). */
+int gsplat_context_features_backward(gsplat_context *ctx, int num_gaussians, int channels,
+                                     const float *features /* [N,C], global order */,
+                                     const float *grad_map /* [H,W,C] */, void *stream);
 
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384

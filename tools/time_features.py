@@ -1,7 +1,7 @@
-"""The two feature-map launches (gsplat_context_render_features, gsplat_context_lift_features) at C = 3, 16 and 64 by
-events on a workload's recorded forward, beside the accumulate_contributions call on the same forward (the same walk,
-reduced per gaussian) and the context's own render_forward stage (per-stage timing).  Warm: 10 calls before the 50 that
-count; medians.
+"""The three feature-map launches (gsplat_context_render_features, gsplat_context_lift_features,
+gsplat_context_features_backward) at C = 3, 16 and 64 by events on a workload's recorded forward, beside the
+accumulate_contributions call on the same forward (the same walk, reduced per gaussian) and the context's own
+render_forward and render_backward stages (per-stage timing).  Warm: 10 calls before the 50 that count; medians.
 
 usage: python tools/time_features.py [workload ...]   (default: config3, 1e6 gaussians at 1920x1080; JSON lines on stdout)"""
 import importlib
@@ -56,6 +56,20 @@ def run(name):
         image, lifted = torch.empty(H, W, C, device="cuda"), torch.zeros(N, C, device="cuda")
         out[f"render_features_C{C}_us"] = round(by_events(lambda: ctx.render_features(feats, out=image)), 2)
         out[f"lift_features_C{C}_us"] = round(by_events(lambda: ctx.lift_features(fmap, lifted)), 2)
+    # the feature map's gradient with respect to the geometry, behind a compositing backward of the same forward (which
+    # is timed by the context's own render_backward stage, beside it)
+    gi = torch.as_tensor(scene.make_grad_image(W, H)).cuda()
+    ctx.set_timing(True, stages=("render_backward",))
+    for _ in range(30):
+        ctx.rasterize_image(dp, dc, c, 0.0, L)
+        ctx.backward_render(gi, 0.0)
+    torch.cuda.synchronize()
+    out["render_backward_us"] = round(ctx.get_timing()["render_backward"][0] * 1e3, 2)
+    ctx.set_timing(False)
+    for C in CHANNELS:
+        feats = torch.as_tensor(rng.uniform(-1, 1, (N, C)).astype(np.float32)).cuda()
+        gmap = torch.as_tensor(rng.uniform(-1, 1, (H, W, C)).astype(np.float32)).cuda()
+        out[f"features_backward_C{C}_us"] = round(by_events(lambda: ctx.features_backward(feats, gmap)), 2)
     print(json.dumps(out), flush=True)
 
 
