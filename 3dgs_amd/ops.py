@@ -288,6 +288,93 @@ def normal_smoothness_loss(normal, image, weight, grad_normal, edge_scale=1.0, a
     return float(out.item()) if blocking else None
 
 
+def _fmap(t, name, shape=None):
+    """An [H,W,C] float32 device feature map (or a gradient or target of one), 1 <= C <= 512; None stays None."""
+    if t is None:
+        return None
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+            or t.dim() != 3 or not 1 <= t.shape[2] <= 512 or (shape is not None and tuple(t.shape) != tuple(shape))):
+        raise ValueError(f"{name} must be a contiguous [H,W,C] float32 device tensor, 1 <= C <= 512"
+                         + (f", of shape {tuple(shape)}" if shape else ""))
+    return t
+
+
+def _pixel_map(t, name, dtype, shape):
+    """An [H,W] device map of `dtype` (labels: int32, validity: uint8); None stays None."""
+    if t is None:
+        return None
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()
+            or tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name} must be a contiguous {tuple(shape)} {dtype} device tensor")
+    return t
+
+
+def feature_ce_loss(fmap, labels, weight, grad_map, accumulate=False, blocking=False):
+    """Softmax cross-entropy of a feature map ([H,W,C], the channels as logits: RasterContext.render_features) against
+    labels ([H,W] int32; a pixel takes part when 0 <= label < C, every other label is ignored): weight x the sum over those
+    pixels of logsumexp - the label's logit, divided by ALL H x W pixels; grad_map ([H,W,C] or None) gets weight / P x
+    (softmax - onehot) there and exactly 0 elsewhere, overwritten or, with accumulate=True, added to
+    (gsplat_feature_ce_loss).  blocking=True returns the loss (a read-back), otherwise None."""
+    fmap = _fmap(fmap, "fmap")
+    if labels is None:
+        raise ValueError("labels is required")
+    H, W, C = fmap.shape
+    out = torch.empty(1, dtype=torch.float32, device=fmap.device) if blocking else None
+    check(_lib.load().gsplat_feature_ce_loss(_p(fmap), _p(_pixel_map(labels, "labels", torch.int32, (H, W))), int(H), int(W),
+                                             int(C), float(weight), int(bool(accumulate)),
+                                             _p(_fmap(grad_map, "grad_map", (H, W, C))), _p(out), _stream()))
+    return float(out.item()) if blocking else None
+
+
+def _feature_target_loss(fn, fmap, target, valid, weight, grad_map, accumulate, blocking):
+    fmap = _fmap(fmap, "fmap")
+    if target is None:
+        raise ValueError("target is required")
+    H, W, C = fmap.shape
+    out = torch.empty(1, dtype=torch.float32, device=fmap.device) if blocking else None
+    check(fn(_p(fmap), _p(_fmap(target, "target", (H, W, C))), _p(_pixel_map(valid, "valid", torch.uint8, (H, W))), int(H),
+             int(W), int(C), float(weight), int(bool(accumulate)), _p(_fmap(grad_map, "grad_map", (H, W, C))), _p(out),
+             _stream()))
+    return float(out.item()) if blocking else None
+
+
+def feature_l1_loss(fmap, target, weight, grad_map, valid=None, accumulate=False, blocking=False):
+    """weight x the mean over all H x W x C elements of |fmap - target| on the pixels whose byte of `valid` ([H,W] uint8;
+    None: every pixel) is set; grad_map gets weight / (P C) x sign(fmap - target) there (sign(0) = 0) and 0 elsewhere,
+    overwritten or added to (gsplat_feature_l1_loss).  blocking=True returns the loss (a read-back), otherwise None."""
+    return _feature_target_loss(_lib.load().gsplat_feature_l1_loss, fmap, target, valid, weight, grad_map, accumulate, blocking)
+
+
+def feature_cosine_loss(fmap, target, weight, grad_map, valid=None, accumulate=False, blocking=False):
+    """weight x the sum over the valid pixels with a non-zero map row f and a non-zero target row t of 1 - f.t / (|f||t|),
+    divided by all H x W pixels; grad_map gets the gradient through the normalisation of f there and exactly 0 elsewhere,
+    overwritten or added to (gsplat_feature_cosine_loss).  blocking=True returns the loss (a read-back), otherwise None."""
+    return _feature_target_loss(_lib.load().gsplat_feature_cosine_loss, fmap, target, valid, weight, grad_map, accumulate,
+                                blocking)
+
+
+def feature_adam_step(compact_to_global, num_culled, features, exp_avg, exp_avg_sq, grad_global, lr, b1, b2, eps, bias1,
+                      bias2):
+    """The Adam step of the feature column on the rows a view saw (gsplat_feature_adam_step): features, exp_avg,
+    exp_avg_sq and grad_global are [N,C] float32 in global gaussian order, compact_to_global the forward's int32 row map
+    with at least num_culled entries.  The rows compact_to_global names are updated in place from their rows of
+    grad_global -- the element step of gsplat_optimizer_step, bit for bit -- and those gradient rows are zeroed; no other
+    row of any of the four is read or written."""
+    M = int(num_culled)
+    if features.dim() != 2 or not 1 <= features.shape[1] <= 512:
+        raise ValueError("features must be [N,C] with 1 <= C <= 512")
+    for name, t in (("features", features), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq), ("grad_global", grad_global)):
+        if _f32(t, name).shape != features.shape:
+            raise ValueError(f"{name} must be shaped as features, {tuple(features.shape)}")
+    if M < 0 or M > features.shape[0]:
+        raise ValueError("num_culled must lie in 0 .. N")
+    if M and (compact_to_global is None or compact_to_global.dtype != torch.int32 or compact_to_global.numel() < M):
+        raise ValueError("compact_to_global must be int32 with at least num_culled entries")
+    check(_lib.load().gsplat_feature_adam_step(_p(compact_to_global) if M else None, M, int(features.shape[1]),
+                                               _p(features), _p(exp_avg), _p(exp_avg_sq), _p(grad_global), float(lr),
+                                               float(b1), float(b2), float(eps), float(bias1), float(bias2), _stream()))
+
+
 def compute_psnr(predicted_data, gt_data, rows, cols):
     out = ctypes.c_float(0.0)
     check(_lib.load().gsplat_compute_psnr(_p(predicted_data), _p(gt_data), rows, cols, ctypes.byref(out), _stream()))

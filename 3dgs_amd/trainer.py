@@ -18,7 +18,7 @@ import torch
 
 from . import ops, raster
 from .dist import TorchComm, ViewShardedStep
-from .optimizer import AdamOptimizer, DEFAULT_LR
+from .optimizer import B1, B2, EPS, AdamOptimizer, DEFAULT_LR
 from .rows import MOMENT, PARAM, STAT, RowTable
 
 DISTORTION_WEIGHT = 10.0  # the default of config key distortion_weight (README, "Depth regularisers")
@@ -83,7 +83,25 @@ DEFAULT_CONFIG = dict(
     # Their gradient goes through ops.depth_to_normal_backward into the depth and opacity maps' gradients, beside the two
     # terms above.  The context renders depth as for those (inverse as distortion_inverse).  One rank only.
     normal_prior=False, normal_prior_weight=NORMAL_PRIOR_WEIGHT, normal_smooth=False,
-    normal_smooth_weight=NORMAL_SMOOTH_WEIGHT, normal_edge_scale=1.0, normal_start=3000, normal_alpha_min=0.5)
+    normal_smooth_weight=NORMAL_SMOOTH_WEIGHT, normal_edge_scale=1.0, normal_start=3000, normal_alpha_min=0.5,
+    # features: C > 0 gives every gaussian a row of C trainable channels (Trainer.features: a column of the row table with
+    # both Adam moments, carried by every row edit; initial value: Trainer(..., features=), default zeros).  From iteration
+    # feature_start on, a view given as (camera, image, depth target or None, normal prior or None, feature target) also
+    # renders the column (RasterContext.render_features) and adds feature_weight x
+    #   feature_loss "ce":     the softmax cross-entropy of the map's channels against the target, an [H,W] int32 label map
+    #                          (a label outside 0 .. C-1 is ignored), over all pixels (ops.feature_ce_loss);
+    #   feature_loss "l1":     the mean of |map - target| for an [H,W,C] float32 target, or a pair (target, valid) with an
+    #                          [H,W] uint8 validity map (ops.feature_l1_loss);
+    #   feature_loss "cosine": the mean of 1 - cos(map, target) over the valid pixels where neither is zero
+    #                          (ops.feature_cosine_loss).
+    # The loss's gradient map is lifted onto the column (RasterContext.lift_features) and the rows the view saw take an
+    # Adam step at feature_lr (ops.feature_adam_step) behind the optimizer step of the other groups.  feature_geometry:
+    # the loss also reaches opacity, conic and position (features_backward inside whichever backward the iteration runs);
+    # off, the image term's calls are exactly those of a run without the key.  Views without a target skip the term.  One
+    # rank only.  feature_lr: README, "Training a feature field", has the numbers behind the default.
+    features=0, feature_loss="ce", feature_weight=1.0, feature_start=0, feature_lr=0.0025, feature_geometry=False)
+
+FEATURE_LOSSES = ("ce", "l1", "cosine")
 
 
 def _logit(p):
@@ -126,9 +144,11 @@ class Trainer:
     """params: dict of device tensors (xyz rgb opacity scale quaternion, optionally sh) as gsplat_initialize_gaussians
     returns them; views: list of (camera dict for raster.device_camera, ground-truth image tensor [H,W,3] on device) or,
     for config key depth_prior, (camera, image, inverse-depth target [H,W] float32 on device) or, for config key
-    normal_prior, (camera, image, that target or None, normal prior [H,W,3] float32 on device)."""
+    normal_prior, (camera, image, that target or None, normal prior [H,W,3] float32 on device) or, for config key features,
+    (camera, image, that target or None, that prior or None, feature target); features: the initial [N,C] float32 feature
+    column of config key features (default: zeros)."""
 
-    def __init__(self, params, views, config=None, scene_extent=1.0, seed=0, exchange="split", comm=None):
+    def __init__(self, params, views, config=None, scene_extent=1.0, seed=0, exchange="split", comm=None, features=None):
         """With an initialised torch.distributed group of W > 1 ranks the loop is view-sharded: every
         rank holds the same parameters and the same seed, one iteration = W training views (rank r takes the r-th of
         the iteration's W draws), the per-gaussian gradients and |grad_uv| are summed over the ranks
@@ -168,6 +188,18 @@ class Trainer:
                                  "gradient in absgrad mode")
         if (self.cfg["normal_prior"] or self.cfg["normal_smooth"]) and self.world > 1:
             raise ValueError("normal_prior / normal_smooth train on one rank: the view-sharded step takes no depth gradients")
+        if self.feature_channels:
+            if self.world > 1:
+                raise ValueError("features train on one rank: the view-sharded step has no place for the feature column")
+            if not 1 <= self.feature_channels <= 512:
+                raise ValueError("features must be 0 (off) or a channel count in 1 .. 512")
+            if self.cfg["feature_loss"] not in FEATURE_LOSSES:
+                raise ValueError("feature_loss must be one of %s" % (FEATURE_LOSSES,))
+        elif features is not None:
+            raise ValueError("a feature tensor needs config key features = its channel count")
+        self._feat = None        # (features, exp_avg, exp_avg_sq), [N,C] each: the row table's feature column (_install)
+        self._feat_grad = None   # [capacity,C]: dL/d features in global order, all zero between two steps
+        self._feat_maps = {}     # (H, W) -> (feature map, dL/d feature map), [H,W,C] each, allocated once
         self._depth_maps = {}  # (H, W) -> the three gradient maps (dL/d alpha, dL/d depth, dL/d depth2), allocated once
         self._normal_maps = {}  # (H, W) -> (normal map, dL/d normal), [H,W,3] each, allocated once (normal_prior / _smooth)
         self._intrinsics = {}   # id(camera dict) -> (camera, ops.pixel_intrinsics of it): read from the device once
@@ -192,12 +224,20 @@ class Trainer:
         H = max(int(v[0]["height"]) for v in views)
         self.ctx = self._new_context(max(n, 1), W, H)
         self.ctx_capacity = n
-        self._install(RowTable.fresh(self.params))
+        self._install(RowTable.fresh(self.params, self._initial_features(features, n)))
         self.history = []
         self.contribution_prunes = []  # (iteration, gaussians removed) of every scheduled prune_by_contribution
         self._set_filter3d(self.ctx)
 
     # ------------------------------------------------------------------ state
+    _feat = None       # (a run without config key features has no column and no accumulator)
+    _feat_grad = None
+
+    @property
+    def feature_channels(self):
+        """C of config key features; 0: off."""
+        return int(self.cfg["features"])
+
     @property
     def num_gaussians(self):
         return int(self.params["xyz"].shape[0])
@@ -205,7 +245,28 @@ class Trainer:
     def _rows(self):
         """Everything that has a row per gaussian, as it stands."""
         o = self.opt
-        return RowTable(self.params, o.exp_avg, o.exp_avg_sq, o.uv_grad_accum, o.grad_accum_dur)
+        return RowTable(self.params, o.exp_avg, o.exp_avg_sq, o.uv_grad_accum, o.grad_accum_dur, self._feat)
+
+    def _initial_features(self, features, n):
+        """The feature column a run starts with (config key features; None when it is off): the caller's [N,C] tensor,
+        or zeros."""
+        C = self.feature_channels
+        if not C:
+            return None
+        dev = self.params["xyz"].device
+        if features is None:
+            return torch.zeros(n, C, dtype=torch.float32, device=dev)
+        if (not isinstance(features, torch.Tensor) or features.dtype != torch.float32 or features.device != dev
+                or tuple(features.shape) != (n, C)):
+            raise ValueError("features must be a float32 [%d,%d] tensor on %s: one row per gaussian, config key features "
+                             "channels" % (n, C, dev))
+        return features.contiguous()
+
+    @property
+    def features(self):
+        """The feature column ([N,C] float32 device tensor, one row per gaussian in the current order: what
+        render_features, feature_gradients and lift_maps take); None when config key features is off."""
+        return None if self._feat is None else self._feat[0]
 
     def _install(self, rows):
         """Make `rows` (a RowTable) the run's state: the parameters, the SH degree their `sh` column has, and an
@@ -216,7 +277,13 @@ class Trainer:
         l_max = math.isqrt(sh.shape[1] + 1) - 1 if sh.dim() == 3 else -1
         if tuple(sh.shape[1:]) != ((l_max + 1) ** 2 - 1, 3):
             raise ValueError("sh is %s: not the coefficients of an SH degree" % (tuple(sh.shape),))
+        if (rows.features is not None) != bool(self.feature_channels) or \
+                (rows.features is not None and rows.features[0].shape[1] != self.feature_channels):
+            raise ValueError("the table's feature column does not match config key features = %d" % self.feature_channels)
         self.l_max = l_max
+        self._feat = rows.features
+        if self._feat_grad is not None and self._feat_grad.shape[0] < rows.num_rows:
+            self._feat_grad = None  # (all zero between steps, whatever the row order: only its size follows the rows)
         self.params = dict(rows.params)
         self.opt = AdamOptimizer({g: self.params[g] for g in rows.exp_avg}, self.l_max, lr_config=self.cfg,
                                  scene_extent=self.scene_extent,
@@ -369,9 +436,63 @@ class Trainer:
         self._refresh_filter3d(it)
         return it, bg, self._context_for(self.num_gaussians)
 
-    def train_step(self, cam, gt_image, want_loss=True, depth_target=None, normal_target=None):
+    def _feature_target(self, target, H, W):
+        """A view's feature target as the configured loss takes it -> (target, valid or None); ValueError otherwise."""
+        C, kind = self.feature_channels, self.cfg["feature_loss"]
+        valid = None
+        if kind != "ce" and isinstance(target, (tuple, list)):
+            if len(target) != 2:
+                raise ValueError("a feature target with a validity map is the pair (target, valid)")
+            target, valid = target
+        want = (torch.int32, (H, W)) if kind == "ce" else (torch.float32, (H, W, C))
+        if not isinstance(target, torch.Tensor) or target.dtype != want[0] or tuple(target.shape) != want[1] or not target.is_cuda:
+            raise ValueError("the feature target of loss '%s' must be a %s device tensor of shape %s" % (kind, want[0], want[1]))
+        if valid is not None and (not isinstance(valid, torch.Tensor) or valid.dtype != torch.uint8
+                                  or tuple(valid.shape) != (H, W) or not valid.is_cuda):
+            raise ValueError("the validity map of a feature target must be a uint8 device tensor of shape %s" % ((H, W),))
+        return target.contiguous(), None if valid is None else valid.contiguous()
+
+    def _feature_loss(self, fmap, target, valid, weight, grad_map, blocking=False):
+        kind = self.cfg["feature_loss"]
+        if kind == "ce":
+            return ops.feature_ce_loss(fmap, target, weight, grad_map, blocking=blocking)
+        fn = ops.feature_l1_loss if kind == "l1" else ops.feature_cosine_loss
+        return fn(fmap, target, weight, grad_map, valid=valid, blocking=blocking)
+
+    def _feature_term(self, ctx, it, H, W, feature_target):
+        """The feature term of this iteration (config key features): the column rendered through the forward that just
+        ran, the loss's gradient map, and that map lifted into the all-zero accumulator -> (features, grad_map) for the
+        backward and the step, or None when the term is not active (nothing is launched or allocated then)."""
+        c = self.cfg
+        if not self.feature_channels or feature_target is None or it < int(c["feature_start"]):
+            return None
+        target, valid = self._feature_target(feature_target, H, W)
+        feats, C, dev = self._feat[0], self.feature_channels, self.params["xyz"].device
+        maps = self._feat_maps.get((H, W))
+        if maps is None:
+            maps = self._feat_maps[(H, W)] = tuple(torch.empty(H, W, C, dtype=torch.float32, device=dev) for _ in range(2))
+        fmap, grad_map = maps
+        n = self.num_gaussians
+        if self._feat_grad is None:
+            self._feat_grad = torch.zeros(max(n, self.ctx_capacity), C, dtype=torch.float32, device=dev)
+        ctx.render_features(feats, out=fmap)
+        w = float(c["feature_weight"])
+        self._feature_loss(fmap, target, valid, w, grad_map)
+        ctx.lift_features(grad_map, self._feat_grad[:n])
+        self.last_regularisers["feature"] = w
+        return feats, grad_map
+
+    def _feature_step(self, it, fwd):
+        """The feature column's Adam step on the rows the view saw, from the accumulator (which is all zero again after)."""
+        f, m, v = self._feat
+        b1c, b2c = self.opt.bias_corrections(it)
+        ops.feature_adam_step(fwd["compact_to_global"], int(fwd["num_culled"]), f, m, v, self._feat_grad[:f.shape[0]],
+                              float(self.cfg["feature_lr"]), B1, B2, EPS, b1c, b2c)
+
+    def train_step(self, cam, gt_image, want_loss=True, depth_target=None, normal_target=None, feature_target=None):
         """depth_target: this view's inverse-depth prior (config key depth_prior), or None; normal_target: its normal prior
-        (config key normal_prior), or None."""
+        (config key normal_prior), or None; feature_target: its feature target (config key features: an [H,W] int32 label
+        map for feature_loss "ce", an [H,W,C] float32 map or (map, [H,W] uint8 validity) for "l1" / "cosine"), or None."""
         if self.world > 1:
             return self._train_step_sharded(cam, gt_image, want_loss)
         c = self.cfg
@@ -393,6 +514,13 @@ class Trainer:
         # row as it is
         dmaps = self._depth_regularisers(fwd, it, H, W, depth_target, cam, gt_image, normal_target) \
             if self._depth_keys() else {}
+        # the feature term (config key features; None when it is off, not yet started or the view has no target: no launch):
+        # the backward takes (features, grad_map) only with feature_geometry -- without it its calls are the plain ones
+        if self.feature_channels and not self._depth_keys():
+            self.last_regularisers = {}
+        fterm = self._feature_term(ctx, it, H, W, feature_target) if self.feature_channels else None
+        if fterm is not None and c["feature_geometry"]:
+            dmaps = dict(dmaps, feature_grads=fterm)
         fused_adam = self.fused_adam  # (0 with antialiased, filter3d or mcmc: decided in __init__)
         if fused_adam == 3:
             # r06: the SH group's step in a kernel that reads the coefficient rows once (update + the sums the position
@@ -418,6 +546,8 @@ class Trainer:
             if c["mcmc"]:
                 ops.mcmc_add_noise(p["xyz"], p["opacity"], p["scale"], p["quaternion"],
                                    float(c["mcmc_noise_lr"]) * self.opt.learning_rates(it)["xyz"], self._mcmc_seed(it))
+        if fterm is not None:
+            self._feature_step(it, fwd)
         self.iter += 1
         return loss
 
@@ -490,6 +620,8 @@ class Trainer:
                 extra["depth_target"] = self.views[v][2]
             if len(self.views[v]) > 3 and self.views[v][3] is not None:
                 extra["normal_target"] = self.views[v][3]
+            if len(self.views[v]) > 4 and self.views[v][4] is not None:  # (config key features)
+                extra["feature_target"] = self.views[v][4]
             want = bool(loss_every) and (self.iter % loss_every == 0 or (log_every and (self.iter + 1) % log_every == 0))
             loss = self.train_step(cam, gt, want_loss=want, **extra)
             if eval_every and (self.iter - 1) % eval_every == 0 and eval_views:
@@ -516,6 +648,43 @@ class Trainer:
         finally:
             ctx.set_render_only(False)
         return total / len(views)
+
+    def evaluate_features(self, views=None):
+        """The feature term over `views` (default: the training views) that carry a feature target, at feature_weight 1 and
+        background 0 on the render-only context: dict(loss=the mean of the configured loss over those views, views=their
+        number) and, for feature_loss "ce", accuracy=the share of the labelled pixels (0 <= label < C) of all those views
+        whose largest channel is their label.  None when no view has a target.  Evaluation only: the accuracy is torch."""
+        if not self.feature_channels:
+            raise ValueError("evaluate_features needs config key features")
+        views = [v for v in (self.views if views is None else views) if len(v) > 4 and v[4] is not None]
+        if not views:
+            return None
+        ctx = self._context_for(self.num_gaussians)
+        total, hits, labelled = 0.0, 0, 0
+        ctx.set_render_only(True)
+        try:
+            for v in views:
+                cam = v[0]
+                H, W = int(cam["height"]), int(cam["width"])
+                target, valid = self._feature_target(v[4], H, W)
+                try:
+                    ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
+                    fmap = ctx.render_features(self._feat[0])
+                except Exception as e:  # no gaussian in view: the map is zero
+                    if getattr(e, "code", None) != -5:
+                        raise
+                    fmap = torch.zeros(H, W, self.feature_channels, dtype=torch.float32, device=target.device)
+                total += self._feature_loss(fmap, target, valid, 1.0, None, blocking=True)
+                if self.cfg["feature_loss"] == "ce":
+                    on = (target >= 0) & (target < self.feature_channels)
+                    hits += int(((fmap.argmax(-1) == target) & on).sum().item())
+                    labelled += int(on.sum().item())
+        finally:
+            ctx.set_render_only(False)
+        out = dict(loss=total / len(views), views=len(views))
+        if self.cfg["feature_loss"] == "ce":
+            out["accuracy"] = hits / labelled if labelled else float("nan")
+        return out
 
     def render_normals(self, cam, alpha_min=None):
         """The [H,W,3] normal map of the current gaussians from `cam` (ops.depth_to_normal on a render-only forward at
@@ -570,8 +739,9 @@ class Trainer:
         no background term).  Nothing is differentiated here: feature_gradients returns the gradients of a loss on the
         map with respect to the gaussians and the features.
 
-        `features` is the caller's tensor, not a column of the trainer's row table: whatever changes the set or the
-        order of the gaussians (densification, pruning, relocation, the Morton re-order) invalidates it."""
+        A tensor of the caller's own is not a column of the trainer's row table: whatever changes the set or the order of
+        the gaussians (densification, pruning, relocation, the Morton re-order) invalidates it.  The trainer's own
+        column (config key features: Trainer.features) follows every such edit and may be passed here."""
         if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] != self.num_gaussians:
             raise ValueError("features must be an [N,C] tensor with one row per gaussian (N = %d)" % self.num_gaussians)
         ctx = self._context_for(self.num_gaussians)
@@ -697,7 +867,7 @@ class Trainer:
         sh = ops.expand_sh(rows.params["sh"], old)
         m, v = (ops.expand_sh(mom["sh"], old) if old else torch.zeros_like(sh) for mom in (rows.exp_avg, rows.exp_avg_sq))
         self._install(RowTable(dict(rows.params, sh=sh), dict(rows.exp_avg, sh=m), dict(rows.exp_avg_sq, sh=v),
-                               rows.uv_grad_accum, rows.grad_accum_dur))
+                               rows.uv_grad_accum, rows.grad_accum_dur, rows.features))
 
     def adaptive_density_step(self):  # cuda/trainer.cu:518-779
         c, n = self.cfg, self.num_gaussians
@@ -752,6 +922,11 @@ class Trainer:
             kept, row = _compact_rows(t, keep, keep_n), tuple(t.shape[1:])
             if kind == MOMENT:  # kept rows keep their moments, new rows start at zero (cuda/trainer.cu:703-742)
                 return torch.cat([kept, t.new_zeros((n_add,) + row)], 0)
+            if g == "features":
+                # the kernels know nothing of the column: a clone takes its source's row, both children of a split their
+                # parent's, in the kernels' row order -- clone k is the k-th flagged gaussian (write_ids), the children
+                # of the k-th flagged split are rows 2 k and 2 k + 1 (gs_density.hip)
+                return torch.cat([kept, t[clone.bool()], t[split.bool()].repeat_interleave(2, 0)], 0)
             return torch.cat([kept, clones[g].reshape((n_clone,) + row), splits[g].reshape((2 * n_split,) + row)], 0)
 
         self._install(self._rows().map(relayout))

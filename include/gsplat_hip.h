@@ -706,6 +706,48 @@ int gsplat_context_features_backward(gsplat_context *ctx, int num_gaussians, int
                                      const float *features /* [N,C], global order */,
                                      const float *grad_map /* [H,W,C] */, void *stream);
 
+/* Training a per-gaussian feature field (no ABI bump: new entry points only; gs_featloss.hip): three losses on a feature
+ * map and the feature column's optimizer step.  A map is [rows, cols, channels] float on the device, channel-contiguous
+ * as gsplat_context_render_features writes it, 1 <= channels <= 512, P = rows x cols.  As for the depth and normal
+ * losses above: every pixel is evaluated in double from the float maps and rounded to float once; grad_map (may be NULL)
+ * is overwritten, or added to when `accumulate` is set; loss_out (may be NULL; a device float) is overwritten with the
+ * sum reduced in double in a fixed order; no atomics, two runs give the same bits.
+ *   gsplat_feature_ce_loss      softmax cross-entropy with the channels as logits and labels int32 [rows, cols]: a pixel
+ *                               takes part when 0 <= label < channels;
+ *                                 loss = weight / P x sum_p (logsumexp(map[p, :]) - map[p, label_p])
+ *                                 grad = weight / P x (softmax(map[p, :]) - onehot(label_p))
+ *                               the maximum is subtracted before the (double) exponentials.  Every other label (negative:
+ *                               "ignore"; channels or more: out of range) adds nothing to the loss and gets a gradient of
+ *                               exactly 0 in every channel;
+ *   gsplat_feature_l1_loss      loss = weight / (P channels) x sum |map - target| over the valid pixels, target [rows, cols,
+ *                               channels], valid uint8 [rows, cols] (non-zero: valid) or NULL (every pixel);
+ *                               grad = weight / (P channels) x sign(map - target), sign(0) = 0, 0 at the other pixels;
+ *   gsplat_feature_cosine_loss  loss = weight / P x sum (1 - f.t / (|f||t|)) over the valid pixels with |f| > 0 and |t| > 0
+ *                               (f = map[p, :], t = target[p, :]); the gradient goes through the normalisation of f:
+ *                               grad = -weight / P x (t - (f.t / |f|^2) f) / (|f||t|); exactly 0 at the other pixels.
+ * Refused with GSPLAT_ERR_INVALID_ARG before anything is launched: a non-positive size, channels outside 1..512, a NULL
+ * map, labels or target, grad_map and loss_out both NULL.
+ *   gsplat_feature_adam_step    gsplat_optimizer_step for one group of stride `channels` whose gradient lies in GLOBAL
+ *                               order (where gsplat_context_lift_features adds it): for every j < num_culled the row
+ *                               compact_to_global[j] of features, exp_avg and exp_avg_sq ([N, channels]) takes the Adam
+ *                               step of gsplat_optimizer_step (the same device function, bit for bit) on the same row of
+ *                               grad_global, and that gradient row is then set to zero -- an accumulator that was all
+ *                               zero before the view's lift is all zero again (lift_features only touches gaussians the
+ *                               forward composited, a subset of the rows the view saw).  Rows the view did not see are
+ *                               neither read nor written, in any of the four arrays.  num_culled == 0 launches nothing. */
+int gsplat_feature_ce_loss(const float *map, const int *labels /* [rows, cols] */, int rows, int cols, int channels,
+                           float weight, int accumulate, float *grad_map, float *loss_out, void *stream);
+int gsplat_feature_l1_loss(const float *map, const float *target, const unsigned char *valid /* [rows, cols] or NULL */,
+                           int rows, int cols, int channels, float weight, int accumulate, float *grad_map,
+                           float *loss_out, void *stream);
+int gsplat_feature_cosine_loss(const float *map, const float *target, const unsigned char *valid /* [rows, cols] or NULL */,
+                               int rows, int cols, int channels, float weight, int accumulate, float *grad_map,
+                               float *loss_out, void *stream);
+int gsplat_feature_adam_step(const int *compact_to_global, int num_culled, int channels,
+                             float *features, float *exp_avg, float *exp_avg_sq /* [N, channels], global order */,
+                             float *grad_global /* [N, channels], global order */, float lr, float b1, float b2,
+                             float eps, float bias1, float bias2, void *stream);
+
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
  * tiles, stable radix sorts on (depth bits, tile).  1 / 2 force one route.  Both produce identical lists. */
