@@ -237,6 +237,9 @@ SIGNATURES = {
     "gsplat_feature_l1_loss": (_I, [_P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P]),
     "gsplat_feature_cosine_loss": (_I, [_P, _P, _P, _I, _I, _I, _F, _I, _P, _P, _P]),
     "gsplat_feature_adam_step": (_I, [_P, _I, _I, _P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _P]),
+    "gsplat_bilagrid_slice": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
+    "gsplat_bilagrid_slice_backward": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "gsplat_bilagrid_tv_loss": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _P]),
     "gsplat_context_set_absgrad": (_I, [_P, _I]),
     "gsplat_context_set_compact_lists": (_I, [_P, _I]),
     "gsplat_context_absgrad_uv": (_I, [_P, _P, _P]),

@@ -130,6 +130,7 @@ enum ScratchSlot {
   SCR_COUNTS = 0, SCR_OFFSETS, SCR_KEYS_A, SCR_KEYS_B, SCR_VALS_B, SCR_TEMP, SCR_SPLATS, SCR_MISC, SCR_GRADROWS,
   SCR_LOSS_MU, SCR_LOSS_S1, SCR_LOSS_S12, SCR_LOSS_ACC,
   SCR_DEPTH_LOSS,  // gsplat_distortion_loss / gsplat_depth_prior_loss: the blocks' partial sums (doubles)
+  SCR_BILAGRID,    // gsplat_bilagrid_slice_backward: the pixel tiles' partial sums of dL/d grid (doubles)
   SCR_NUM
 };
 DeviceBuffer &scratch(ScratchSlot slot);

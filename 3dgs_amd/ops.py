@@ -375,6 +375,73 @@ def feature_adam_step(compact_to_global, num_culled, features, exp_avg, exp_avg_
                                                float(b1), float(b2), float(eps), float(bias1), float(bias2), _stream()))
 
 
+def _bilagrid(t, name, shape=None):
+    """A [12,L,Hg,Wg] float32 device bilateral grid (or a gradient of one) -> (tensor, Wg, Hg, L); None stays None."""
+    if t is None:
+        return None
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+            or t.dim() != 4 or t.shape[0] != 12 or (shape is not None and tuple(t.shape) != tuple(shape))):
+        raise ValueError(f"{name} must be a contiguous [12,L,Hg,Wg] float32 device tensor"
+                         + (f" of shape {tuple(shape)}" if shape else ""))
+    return t
+
+
+def identity_bilagrid(grid_w, grid_h, grid_l, views=None, device="cuda"):
+    """The grid that gives every image back: channels 0, 5 and 10 (the diagonal of the 3x4 affine) one, the others zero;
+    [12,L,Hg,Wg], or [views,12,L,Hg,Wg]."""
+    grid = torch.zeros((12, int(grid_l), int(grid_h), int(grid_w)), dtype=torch.float32, device=device)
+    grid[[0, 5, 10]] = 1.0
+    return grid if views is None else grid.unsqueeze(0).repeat(int(views), 1, 1, 1, 1).contiguous()
+
+
+def bilagrid_slice(grid, image, out=None):
+    """The image corrected by a bilateral grid (gsplat_bilagrid_slice): per pixel the 3x4 affine interpolated from `grid`
+    ([12,L,Hg,Wg]) at the pixel's position and luma, applied to its colour; image and out are [H,W,3].  out: the map to
+    write, or None for a new one."""
+    grid = _bilagrid(grid, "grid")
+    image = _map3(image, "image")
+    if grid is None or image is None:
+        raise ValueError("grid and image are required")
+    H, W = image.shape[:2]
+    if out is None:
+        out = torch.empty_like(image)
+    _, L, Hg, Wg = grid.shape
+    check(_lib.load().gsplat_bilagrid_slice(_p(grid), int(Wg), int(Hg), int(L), _p(image), int(H), int(W),
+                                            _p(_map3(out, "out", (H, W))), _stream()))
+    return out
+
+
+def bilagrid_slice_backward(grid, image, grad_out, grad_image=None, grad_grid=None, accumulate_grid=False):
+    """dL/d corrected ([H,W,3]) of bilagrid_slice -> grad_image = dL/d image ([H,W,3] or None; written, never added to;
+    must not be grad_out or image) and grad_grid = dL/d grid ([12,L,Hg,Wg] or None; overwritten, or added to with
+    accumulate_grid=True) (gsplat_bilagrid_slice_backward)."""
+    grid = _bilagrid(grid, "grid")
+    image = _map3(image, "image")
+    if grid is None or image is None or grad_out is None:
+        raise ValueError("grid, image and grad_out are required")
+    H, W = image.shape[:2]
+    _, L, Hg, Wg = grid.shape
+    check(_lib.load().gsplat_bilagrid_slice_backward(
+        _p(grid), int(Wg), int(Hg), int(L), _p(image), _p(_map3(grad_out, "grad_out", (H, W))), int(H), int(W),
+        int(bool(accumulate_grid)), _p(_map3(grad_image, "grad_image", (H, W))),
+        _p(_bilagrid(grad_grid, "grad_grid", grid.shape)), _stream()))
+
+
+def bilagrid_tv_loss(grid, weight, grad_grid, accumulate=False, blocking=False):
+    """The total-variation loss of one bilateral grid: weight x the sum over the three axes of the mean squared difference
+    of the adjacent pairs along the axis (all 12 channels; an axis of one vertex adds 0); grad_grid ([12,L,Hg,Wg] or None)
+    gets the gradient, overwritten or added to (gsplat_bilagrid_tv_loss).  blocking=True returns the loss (a read-back),
+    otherwise None."""
+    grid = _bilagrid(grid, "grid")
+    if grid is None:
+        raise ValueError("grid is required")
+    _, L, Hg, Wg = grid.shape
+    out = torch.empty(1, dtype=torch.float32, device=grid.device) if blocking else None
+    check(_lib.load().gsplat_bilagrid_tv_loss(_p(grid), int(Wg), int(Hg), int(L), float(weight), int(bool(accumulate)),
+                                              _p(_bilagrid(grad_grid, "grad_grid", grid.shape)), _p(out), _stream()))
+    return float(out.item()) if blocking else None
+
+
 def compute_psnr(predicted_data, gt_data, rows, cols):
     out = ctypes.c_float(0.0)
     check(_lib.load().gsplat_compute_psnr(_p(predicted_data), _p(gt_data), rows, cols, ctypes.byref(out), _stream()))

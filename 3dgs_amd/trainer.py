@@ -99,7 +99,20 @@ DEFAULT_CONFIG = dict(
     # the loss also reaches opacity, conic and position (features_backward inside whichever backward the iteration runs);
     # off, the image term's calls are exactly those of a run without the key.  Views without a target skip the term.  One
     # rank only.  feature_lr: README, "Training a feature field", has the numbers behind the default.
-    features=0, feature_loss="ce", feature_weight=1.0, feature_start=0, feature_lr=0.0025, feature_geometry=False)
+    features=0, feature_loss="ce", feature_weight=1.0, feature_start=0, feature_lr=0.0025, feature_geometry=False,
+    # bilagrid: per-view appearance compensation ("Bilateral Guided Radiance Field Processing", Wang et al. 2024; gsplat's
+    # lib_bilagrid).  Every training view owns a bilateral grid of 3x4 colour affines (Trainer.bilagrids
+    # [V,12,L,Hg,Wg], identity at the start, addressed by the view's index in Trainer.views: train_step(view_index=)),
+    # bilagrid_shape = (Wg, Hg, L); (1, 1, 1) is one colour affine per view: exposure and white balance.  From iteration
+    # bilagrid_start on the render is corrected by the view's grid (ops.bilagrid_slice) before the L1 + SSIM loss, the
+    # loss's gradient goes back through it (ops.bilagrid_slice_backward) to the render -- the backward and the optimizer
+    # step see only that dL/d image, in every GSPLAT_FUSED_ADAM mode -- and to the grid, which also takes the gradient of
+    # bilagrid_tv_weight x its total variation (ops.bilagrid_tv_loss) and an Adam step at bilagrid_lr with the bias
+    # corrections of the view's own step count.  The depth, normal and feature terms keep reading the raw forward, and
+    # evaluate() scores the raw render; Trainer.render_corrected gives a training view's corrected one.  One rank only.
+    # The defaults of shape, rate and weight are gsplat's published ones (its bilateral-grid example: a 16 x 16 x 8 grid,
+    # learning rate 2e-3, TV weight 10); nothing here has tuned them.
+    bilagrid=False, bilagrid_shape=(16, 16, 8), bilagrid_lr=0.002, bilagrid_tv_weight=10.0, bilagrid_start=0)
 
 FEATURE_LOSSES = ("ce", "l1", "cosine")
 
@@ -197,6 +210,16 @@ class Trainer:
                 raise ValueError("feature_loss must be one of %s" % (FEATURE_LOSSES,))
         elif features is not None:
             raise ValueError("a feature tensor needs config key features = its channel count")
+        self.bilagrids = None        # [V,12,L,Hg,Wg]: the views' bilateral grids (config key bilagrid; None: off)
+        self._bilagrid_state = None  # (exp_avg, exp_avg_sq as bilagrids, the views' Adam step counts, dL/d grid [12,L,Hg,Wg])
+        self._grad_render = {}       # (H, W) -> dL/d render behind the grid, allocated once per image size
+        if self.cfg["bilagrid"]:
+            if self.world > 1:
+                raise ValueError("bilagrid trains on one rank: the view-sharded step has no place for the views' grids")
+            shape = self.cfg["bilagrid_shape"]
+            if (not isinstance(shape, (tuple, list)) or len(shape) != 3 or not all(isinstance(v, int) for v in shape)
+                    or not (1 <= shape[0] <= 64 and 1 <= shape[1] <= 64 and 1 <= shape[2] <= 16)):
+                raise ValueError("bilagrid_shape must be (Wg, Hg, L) with 1 <= Wg, Hg <= 64 and 1 <= L <= 16")
         self._feat = None        # (features, exp_avg, exp_avg_sq), [N,C] each: the row table's feature column (_install)
         self._feat_grad = None   # [capacity,C]: dL/d features in global order, all zero between two steps
         self._feat_maps = {}     # (H, W) -> (feature map, dL/d feature map), [H,W,C] each, allocated once
@@ -228,6 +251,12 @@ class Trainer:
         self.history = []
         self.contribution_prunes = []  # (iteration, gaussians removed) of every scheduled prune_by_contribution
         self._set_filter3d(self.ctx)
+        if self.cfg["bilagrid"]:
+            Wg, Hg, L = self.cfg["bilagrid_shape"]
+            dev = self.params["xyz"].device
+            self.bilagrids = ops.identity_bilagrid(Wg, Hg, L, views=len(views), device=dev)
+            self._bilagrid_state = (torch.zeros_like(self.bilagrids), torch.zeros_like(self.bilagrids), [0] * len(views),
+                                    torch.empty(12, L, Hg, Wg, dtype=torch.float32, device=dev))
 
     # ------------------------------------------------------------------ state
     _feat = None       # (a run without config key features has no column and no accumulator)
@@ -489,13 +518,33 @@ class Trainer:
         ops.feature_adam_step(fwd["compact_to_global"], int(fwd["num_culled"]), f, m, v, self._feat_grad[:f.shape[0]],
                               float(self.cfg["feature_lr"]), B1, B2, EPS, b1c, b2c)
 
-    def train_step(self, cam, gt_image, want_loss=True, depth_target=None, normal_target=None, feature_target=None):
+    def _bilagrid_view(self, view_index):
+        """The index of a training view as config key bilagrid addresses its grid; ValueError when it names none."""
+        if view_index is None:
+            raise ValueError("config key bilagrid: train_step needs view_index=, the view's index in Trainer.views")
+        v = int(view_index)
+        if not 0 <= v < self.bilagrids.shape[0]:
+            raise ValueError("view_index must lie in 0 .. %d" % (self.bilagrids.shape[0] - 1))
+        return v
+
+    def _bilagrid_step(self, v):
+        """The Adam step of view v's grid from the gradient the iteration left, at the view's own step count."""
+        m, sq, steps, grad = self._bilagrid_state
+        b1c, b2c = self.opt.bias_corrections(steps[v])
+        ops.adam_step(self.bilagrids[v], grad, m[v], sq[v], float(self.cfg["bilagrid_lr"]), B1, B2, EPS, b1c, b2c,
+                      grad.numel(), 1)
+        steps[v] += 1
+
+    def train_step(self, cam, gt_image, want_loss=True, depth_target=None, normal_target=None, feature_target=None,
+                   view_index=None):
         """depth_target: this view's inverse-depth prior (config key depth_prior), or None; normal_target: its normal prior
         (config key normal_prior), or None; feature_target: its feature target (config key features: an [H,W] int32 label
-        map for feature_loss "ce", an [H,W,C] float32 map or (map, [H,W] uint8 validity) for "l1" / "cosine"), or None."""
+        map for feature_loss "ce", an [H,W,C] float32 map or (map, [H,W] uint8 validity) for "l1" / "cosine"), or None;
+        view_index: the view's index in Trainer.views (config key bilagrid, which needs it: the view's grid)."""
         if self.world > 1:
             return self._train_step_sharded(cam, gt_image, want_loss)
         c = self.cfg
+        bview = self._bilagrid_view(view_index) if c["bilagrid"] else None
         it, bg, ctx = self._begin_step()
         p = dict(self.params)
         H, W = int(cam["height"]), int(cam["width"])
@@ -508,7 +557,20 @@ class Trainer:
             return None
         grad_image = self._grad_image_for(H, W, gt_image.device)
         # the loss value is a blocking read-back: only fetched when the caller logs it
-        loss = ops.fused_loss(fwd["image"], gt_image, H, W, float(c["ssim_frac"]), grad_image, blocking=want_loss)
+        bgrid = self.bilagrids[bview] if bview is not None and it >= int(c["bilagrid_start"]) else None
+        if bgrid is None:
+            loss = ops.fused_loss(fwd["image"], gt_image, H, W, float(c["ssim_frac"]), grad_image, blocking=want_loss)
+        else:
+            # config key bilagrid: the loss sees the render corrected by the view's grid; its gradient goes back through
+            # the grid into a second buffer, which is the dL/d image of everything below, and into the grid's gradient
+            grad_corrected, grad_image = grad_image, self._grad_render.get((H, W))
+            if grad_image is None:
+                grad_image = self._grad_render[(H, W)] = torch.empty_like(grad_corrected)
+            corrected = ops.bilagrid_slice(bgrid, fwd["image"], out=grad_image)  # (the buffer is free until the backward)
+            loss = ops.fused_loss(corrected, gt_image, H, W, float(c["ssim_frac"]), grad_corrected, blocking=want_loss)
+            grad_grid = self._bilagrid_state[3]
+            ops.bilagrid_slice_backward(bgrid, fwd["image"], grad_corrected, grad_image, grad_grid)
+            ops.bilagrid_tv_loss(bgrid, float(c["bilagrid_tv_weight"]), grad_grid, accumulate=True)
         # the depth terms (config keys distortion, depth_prior, normal_prior, normal_smooth; {} when none is active: the
         # plain backward, exactly) ride with whichever backward the iteration runs -- the Adam-inside forms take the depth
         # row as it is
@@ -516,8 +578,10 @@ class Trainer:
             if self._depth_keys() else {}
         # the feature term (config key features; None when it is off, not yet started or the view has no target: no launch):
         # the backward takes (features, grad_map) only with feature_geometry -- without it its calls are the plain ones
-        if self.feature_channels and not self._depth_keys():
+        if (self.feature_channels or c["bilagrid"]) and not self._depth_keys():
             self.last_regularisers = {}
+        if bgrid is not None:
+            self.last_regularisers["bilagrid_tv"] = float(c["bilagrid_tv_weight"])
         fterm = self._feature_term(ctx, it, H, W, feature_target) if self.feature_channels else None
         if fterm is not None and c["feature_geometry"]:
             dmaps = dict(dmaps, feature_grads=fterm)
@@ -548,6 +612,8 @@ class Trainer:
                                    float(c["mcmc_noise_lr"]) * self.opt.learning_rates(it)["xyz"], self._mcmc_seed(it))
         if fterm is not None:
             self._feature_step(it, fwd)
+        if bgrid is not None:
+            self._bilagrid_step(bview)
         self.iter += 1
         return loss
 
@@ -622,6 +688,8 @@ class Trainer:
                 extra["normal_target"] = self.views[v][3]
             if len(self.views[v]) > 4 and self.views[v][4] is not None:  # (config key features)
                 extra["feature_target"] = self.views[v][4]
+            if self.cfg["bilagrid"]:
+                extra["view_index"] = v
             want = bool(loss_every) and (self.iter % loss_every == 0 or (log_every and (self.iter + 1) % log_every == 0))
             loss = self.train_step(cam, gt, want_loss=want, **extra)
             if eval_every and (self.iter - 1) % eval_every == 0 and eval_views:
@@ -648,6 +716,21 @@ class Trainer:
         finally:
             ctx.set_render_only(False)
         return total / len(views)
+
+    def render_corrected(self, view_index):
+        """The render of training view `view_index` corrected by its bilateral grid (config key bilagrid): the forward on
+        the render-only context at background 0, as evaluate() renders it, then ops.bilagrid_slice -> [H,W,3]."""
+        if not self.cfg["bilagrid"]:
+            raise ValueError("render_corrected needs config key bilagrid")
+        v = self._bilagrid_view(view_index)
+        cam = self.views[v][0]
+        ctx = self._context_for(self.num_gaussians)
+        ctx.set_render_only(True)
+        try:
+            fwd = ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
+            return ops.bilagrid_slice(self.bilagrids[v], fwd["image"])
+        finally:
+            ctx.set_render_only(False)
 
     def evaluate_features(self, views=None):
         """The feature term over `views` (default: the training views) that carry a feature target, at feature_weight 1 and

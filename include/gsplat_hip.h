@@ -748,6 +748,46 @@ int gsplat_feature_adam_step(const int *compact_to_global, int num_culled, int c
                              float *grad_global /* [N, channels], global order */, float lr, float b1, float b2,
                              float eps, float bias1, float bias2, void *stream);
 
+/* Per-view appearance compensation with a bilateral grid (no ABI bump: new entry points only; gs_bilagrid.hip;
+ * "Bilateral Guided Radiance Field Processing", Wang et al. 2024).  A grid is [12, grid_l, grid_h, grid_w] float on the
+ * device, 1 <= grid_w, grid_h <= 64, 1 <= grid_l <= 16; an image is [rows, cols, 3] float.  For pixel (x, y) with colour r:
+ *   guidance      g  = 0.299 r0 + 0.587 r1 + 0.114 r2
+ *   coordinates   gx = (x + 0.5) / cols x (grid_w - 1), gy = (y + 0.5) / rows x (grid_h - 1),
+ *                 gz = clamp(g, 0, 1) x (grid_l - 1)
+ *   cell, per axis of n vertices:  i0 = min(floor(c), max(n - 2, 0)), i1 = min(i0 + 1, n - 1), t = c - i0
+ *   coefficients  A = the 12 trilinearly interpolated values as a row-major 3x4 matrix (channel = row x 4 + column)
+ *   output        out = A[:, :3] r + A[:, 3]
+ * which is grid_sample(bilinear, align_corners, border padding) of the grid followed by the affine.  A grid whose
+ * channels 0, 5 and 10 are one and the others zero gives the image back; a 1 x 1 x 1 grid is one 3x4 colour affine per view.
+ * As for the depth, normal and feature losses: everything is evaluated in double from the float inputs and every stored
+ * value is rounded to float once.  Inputs must be finite.
+ *   gsplat_bilagrid_slice           out [rows, cols, 3] = the corrected image (out may be image itself).
+ *   gsplat_bilagrid_slice_backward  from grad_out = dL/d out: grad_image (or NULL) = dL/d image, WRITTEN, never added to:
+ *                                   A[:, :3]^T G plus, through the guidance, (sum_rc G_r dA_rc/dgz [r,1]_c) (grid_l - 1)
+ *                                   (0.299, 0.587, 0.114) -- that part is exactly 0 where g <= 0, g >= 1 (the two ends
+ *                                   themselves included, as grid_sample's border padding has it) or grid_l == 1;
+ *                                   grad_grid (or NULL) [12, grid_l, grid_h, grid_w] = sum over the pixels of
+ *                                   wx wy wz G_row [r,1]_col, overwritten, or added to (the once-rounded value) when
+ *                                   accumulate_grid is set.  grad_grid is summed in double at every stage WITHOUT atomics:
+ *                                   per 32 x 32 pixel tile into a slab of the library's scratch, then per grid value over
+ *                                   the tiles in a fixed order -- like out and grad_image it carries the same bits in
+ *                                   every run.  The slab is tiles x (vertices a tile touches) x grid_l x 12 doubles.
+ *   gsplat_bilagrid_tv_loss         loss = weight x sum over the three axes of (the sum over the adjacent pairs along the
+ *                                   axis, all 12 channels, of the squared difference / the number of such pairs); an axis
+ *                                   of one vertex adds 0.  grad_grid (or NULL) gets its gradient, overwritten or added to
+ *                                   with `accumulate`; loss_out (or NULL; a device float) the loss, summed per block and
+ *                                   finished in a fixed order.
+ * Refused with GSPLAT_ERR_INVALID_ARG before anything is launched, and before the device is asked anything: a grid size
+ * outside the limits, a non-positive image size, a NULL grid, image, out or grad_out, both gradient outputs NULL
+ * (grad_grid and loss_out for the TV loss), grad_image overlapping grad_out or image. */
+int gsplat_bilagrid_slice(const float *grid, int grid_w, int grid_h, int grid_l, const float *image, int rows, int cols,
+                          float *out, void *stream);
+int gsplat_bilagrid_slice_backward(const float *grid, int grid_w, int grid_h, int grid_l, const float *image,
+                                   const float *grad_out, int rows, int cols, int accumulate_grid,
+                                   float *grad_image /* or NULL */, float *grad_grid /* or NULL */, void *stream);
+int gsplat_bilagrid_tv_loss(const float *grid, int grid_w, int grid_h, int grid_l, float weight, int accumulate,
+                            float *grad_grid, float *loss_out, void *stream);
+
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
  * tiles, stable radix sorts on (depth bits, tile).  1 / 2 force one route.  Both produce identical lists. */
