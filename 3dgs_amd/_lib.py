@@ -240,6 +240,8 @@ SIGNATURES = {
     "gsplat_bilagrid_slice": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
     "gsplat_bilagrid_slice_backward": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "gsplat_bilagrid_tv_loss": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _P]),
+    "gsplat_vq_assign": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "gsplat_vq_update": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "gsplat_context_set_absgrad": (_I, [_P, _I]),
     "gsplat_context_set_compact_lists": (_I, [_P, _I]),
     "gsplat_context_absgrad_uv": (_I, [_P, _P, _P]),

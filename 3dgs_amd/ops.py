@@ -442,6 +442,103 @@ def bilagrid_tv_loss(grid, weight, grad_grid, accumulate=False, blocking=False):
     return float(out.item()) if blocking else None
 
 
+VQ_MAX_D, VQ_MAX_K = 64, 65536
+
+
+def _vq_rows(t, name, cols=None):
+    """A contiguous [rows, D] float32 device tensor with 1 <= D <= 64 (and D == cols when given)."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+            or t.dim() != 2 or not 1 <= t.shape[1] <= VQ_MAX_D or (cols is not None and t.shape[1] != cols)):
+        raise ValueError(f"{name} must be a contiguous [rows,D] float32 device tensor, 1 <= D <= {VQ_MAX_D}"
+                         + (f", D = {cols}" if cols is not None else ""))
+    return t
+
+
+def _vq_codebook(t, D):
+    t = _vq_rows(t, "codebook", D)
+    if not 1 <= t.shape[0] <= VQ_MAX_K:
+        raise ValueError(f"codebook must have 1 .. {VQ_MAX_K} rows")
+    return t
+
+
+def _vq_column(t, name, n, dtype):
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous()
+            or tuple(t.shape) != (n,)):
+        raise ValueError(f"{name} must be a contiguous [{n}] {dtype} device tensor")
+    return t
+
+
+def vq_assign(x, codebook, index=None, dist=None):
+    """The nearest centroid of every row (gsplat_vq_assign): x [N,D], codebook [K,D] -> index [N] int32 (written into
+    `index` when given).  dist: None, or an [N] float32 tensor that gets the squared distance to the chosen centroid.
+    Ties resolve to the lowest index."""
+    x = _vq_rows(x, "x")
+    N, D = x.shape
+    codebook = _vq_codebook(codebook, D)
+    index = torch.empty(N, dtype=torch.int32, device=x.device) if index is None else _vq_column(index, "index", N, torch.int32)
+    if dist is not None:
+        _vq_column(dist, "dist", N, torch.float32)
+    check(_lib.load().gsplat_vq_assign(_p(x), _p(codebook), int(N), int(D), int(codebook.shape[0]), _p(index), _p(dist),
+                                       _stream()))
+    return index
+
+
+def vq_update(x, index, codebook):
+    """Every centroid becomes the mean of the rows assigned to it, in place (gsplat_vq_update); a centroid without rows
+    keeps its bits.  The rows are ordered by (index, row) with a stable sort: the sums have one order."""
+    x = _vq_rows(x, "x")
+    N, D = x.shape
+    codebook = _vq_codebook(codebook, D)
+    K = codebook.shape[0]
+    _vq_column(index, "index", N, torch.int32)
+    if N:
+        lo, hi = int(index.min()), int(index.max())
+        if lo < 0 or hi >= K:
+            raise ValueError("index must lie in 0 .. K-1")
+    order = torch.sort(index, stable=True).indices.to(torch.int32).contiguous()
+    start = torch.zeros(K + 1, dtype=torch.int32, device=x.device)
+    start[1:] = torch.cumsum(torch.bincount(index, minlength=K), 0)
+    check(_lib.load().gsplat_vq_update(_p(x), _p(order), _p(start), int(N), int(D), int(K), _p(codebook), _stream()))
+    return codebook
+
+
+def vq_fit(x, K, iterations=10, seed=0):
+    """k-means (Lloyd) over the rows of x [N,D] -> (codebook [K,D], index [N] int32, objective per assign).  K is clamped
+    to N.  The initial centroids are the first K rows of a seeded permutation.  Each of `iterations` rounds is an assign,
+    a re-seeding -- every empty cluster, in index order, takes one of the rows with the largest distance (descending,
+    ties by row index) and that row moves to it -- and an update; a last assign makes `index` nearest for the codebook
+    returned.  objective[t] is the sum of the squared distances after assign t (iterations + 1 values, never increasing
+    beyond what the assign's rounding allows).  The same seed reproduces codebook and index bit for bit."""
+    x = _vq_rows(x, "x")
+    N, D = x.shape
+    if not isinstance(K, int) or K < 1:
+        raise ValueError("K must be a positive integer")
+    if N < 1:
+        raise ValueError("x has no rows")
+    if not isinstance(iterations, int) or iterations < 0:
+        raise ValueError("iterations must be a non-negative integer")
+    K = min(K, N)
+    if K > VQ_MAX_K:
+        raise ValueError(f"K must be at most {VQ_MAX_K}")
+    perm = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))[:K]
+    codebook = x[perm.to(x.device)].contiguous()
+    index = torch.empty(N, dtype=torch.int32, device=x.device)
+    dist = torch.empty(N, dtype=torch.float32, device=x.device)
+    objective = []
+    for it in range(iterations + 1):
+        vq_assign(x, codebook, index, dist)
+        objective.append(float(dist.sum(dtype=torch.float64)))
+        if it == iterations:
+            break
+        empty = (torch.bincount(index, minlength=K) == 0).nonzero().flatten()
+        if empty.numel():
+            donors = torch.sort(dist, descending=True, stable=True).indices[:empty.numel()]
+            codebook[empty] = x[donors]
+            index[donors] = empty.to(torch.int32)
+        vq_update(x, index, codebook)
+    return codebook, index, objective
+
+
 def compute_psnr(predicted_data, gt_data, rows, cols):
     out = ctypes.c_float(0.0)
     check(_lib.load().gsplat_compute_psnr(_p(predicted_data), _p(gt_data), rows, cols, ctypes.byref(out), _stream()))

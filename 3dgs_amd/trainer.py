@@ -1105,3 +1105,24 @@ class Trainer:
         q = (q / np.where(norm > 0, norm, 1.0)).astype(np.float32)
         dataset.save_ply(path, p["xyz"], p["rgb"], p["opacity"], p["scale"], np.roll(q, 1, axis=1),
                          p["sh"].reshape(len(p["xyz"]), -1) if self.l_max > 0 else None)
+
+    def save_compressed(self, path, raw=False, codebook_size=65536, iterations=10, seed=0):
+        """The scene as a compressed .npz (compress.py: SH rows vector-quantised into a codebook by ops.vq_fit, the other
+        attributes in 8 or 16 bits), readable with compress.load_scene.  As in save_to_ply the file holds the FUSED scale
+        and opacity under the 3D smoothing filter unless raw=True.  Returns the arrays written, with the k-means
+        objective per assign under "objective" (not part of the file)."""
+        from . import compress
+        params = dict(self.params)
+        if self.cfg["filter3d"] and not raw and self.num_gaussians:
+            params["scale"], params["opacity"] = ops.filter3d_apply(params["scale"], params["opacity"], self.filter3d)
+        p = {k: v.detach().cpu().numpy() for k, v in params.items()}
+        objective = []
+
+        def fit(rows, K, its, sd):  # the rows are on the device already
+            codebook, index, obj = ops.vq_fit(params["sh"].reshape(self.num_gaussians, -1).contiguous(), K,
+                                              iterations=its, seed=sd)
+            objective.extend(obj)
+            return codebook.cpu().numpy(), index.cpu().numpy()
+
+        arrays = compress.save_scene(path, p, fit=fit, codebook_size=codebook_size, iterations=iterations, seed=seed)
+        return dict(arrays, objective=np.asarray(objective, np.float64))

@@ -788,6 +788,30 @@ int gsplat_bilagrid_slice_backward(const float *grid, int grid_w, int grid_h, in
 int gsplat_bilagrid_tv_loss(const float *grid, int grid_w, int grid_h, int grid_l, float weight, int accumulate,
                             float *grad_grid, float *loss_out, void *stream);
 
+/* Vector quantisation of row vectors: the k-means behind the compressed scene export's SH codebook (no ABI bump: new
+ * entry points only; gs_vq.hip; "Compressed 3D Gaussian Splatting", Niedermayr et al. 2024).  x is [N, D] float, codebook
+ * [K, D] float, both on the device, row-major and dense; 1 <= D <= 64, 1 <= K <= 65536, N >= 0 (N = 0: a successful
+ * no-op).  Inputs must be finite.
+ *   gsplat_vq_assign  index[n] = the centroid k with the smallest score s[n,k] = |c_k|^2 - 2 x_n . c_k, which orders the
+ *                     centroids as the squared Euclidean distance does.  The score is a k-ordered float fmaf chain on the
+ *                     f32-input matrix cores (|c_k|^2 first, itself a float chain, then the coordinates in order), so a
+ *                     centroid whose true distance is within ~1.5e-7 x sum_d (x^2 + c^2 + 2 |x c|) of the nearest one's may
+ *                     be returned in its place; exactly equal scores resolve to the LOWEST index.  Every point scans the
+ *                     codebook in a fixed order and nothing is added atomically: two runs give the same bits.
+ *                     dist (or NULL) [N] = sum_d (x_nd - c_{index[n],d})^2 evaluated in double from the floats and
+ *                     rounded to float once -- not the score.
+ *   gsplat_vq_update  order [N] lists the rows sorted by (index, row), start [K + 1] the clusters' offsets into it
+ *                     (start[0] = 0, start[K] = N).  codebook[k] = the mean of x[order[start[k] .. start[k+1])], summed in
+ *                     double by a group of 1 .. 64 lanes per (cluster, coordinate) -- members interleaved over the lanes,
+ *                     the lanes combined by a fixed butterfly; the width is a function of N and K alone -- and rounded to
+ *                     float once.  An empty cluster keeps its centroid's bits.  No atomics: two runs give the same bits.
+ * Refused with GSPLAT_ERR_INVALID_ARG before anything is launched, and before the device is asked anything: D or K outside
+ * the limits, a negative N, and (N > 0) a NULL x, codebook, index, order or start. */
+int gsplat_vq_assign(const float *x, const float *codebook, int N, int D, int K, int *index, float *dist /* or NULL */,
+                     void *stream);
+int gsplat_vq_update(const float *x, const int *order, const int *start, int N, int D, int K, float *codebook,
+                     void *stream);
+
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
  * tiles, stable radix sorts on (depth bits, tile).  1 / 2 force one route.  Both produce identical lists. */
