@@ -244,6 +244,7 @@ SIGNATURES = {
     "gsplat_vq_update": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "gsplat_context_set_absgrad": (_I, [_P, _I]),
     "gsplat_context_set_compact_lists": (_I, [_P, _I]),
+    "gsplat_context_set_dir_sums": (_I, [_P, _I]),
     "gsplat_context_absgrad_uv": (_I, [_P, _P, _P]),
     "gsplat_pack_absgrad_norm": (_I, [_P, _I, _P, _P]),
     "gsplat_context_set_antialiased": (_I, [_P, _I]),

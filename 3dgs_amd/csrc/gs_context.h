@@ -29,6 +29,9 @@ bool no_fwd_segments();
 // GSPLAT_FWD_SEGMENTS_GATE=<x>: the forward splits its long lists when the longest chain exceeds x times the work per
 // resident workgroup (default 3; 0: always)
 double fwd_segments_gate();
+// GSPLAT_NO_DIR_SUMS=1: no forward writes and no backward reads the SH direction sums, whatever the context's switch says
+// (A/B, as GSPLAT_NO_COMPACT_LISTS; gsplat_context_set_dir_sums)
+bool no_dir_sums();
 
 }  // namespace gs
 
@@ -116,6 +119,21 @@ struct gsplat_context {
   gs::DeviceBuffer kept;     // slice-local lists of the kept gaussians (project_cull -> preprocess' compacted walk)
   gs::DeviceBuffer dir_grad;  // [M,3]: sh_adam_dir_kernel -> preprocess_bwd_kernel<L, 3> (gsplat_adam_fused.mode 2)
   gs::DeviceBuffer cam_rows;  // [ceil(M/64),16] doubles: preprocess_bwd_kernel<.., kCamGrad> -> cam_grad_finalize_kernel
+  // The SH direction sums (gsplat_context_set_dir_sums; gs_math.h: sh_dir_sums): [max_gaussians,9], compacted order, written
+  // by preprocess_kernel<.., kDirSums> and read by preprocess_bwd_kernel<.., kDirSums> instead of the SH rows, band 0 and
+  // xyz_c.  Allocated by the first forward that writes them (never by a render-only context).  dir_sums_of names the
+  // forward whose sums the buffer holds: its ticket (0: nobody's) and the inputs the sums were formed from --
+  // a backward reads them only when all of that is the recorded forward's and its own; gsplat_rasterize_image voids the
+  // record before it queues anything, and only the launch of the kernel that writes the sums sets it.
+  gs::DeviceBuffer dir_sums;
+  bool dir_sums_on = true;  // the switch; read by the next forward and by every backward (GSPLAT_NO_DIR_SUMS=1 overrides it)
+  struct DirSumsOf {
+    unsigned long long ticket = 0;
+    const float *xyz = nullptr, *rgb = nullptr, *sh = nullptr, *view = nullptr;
+    float campos[3] = {0.f, 0.f, 0.f};
+  } dir_sums_of;
+  unsigned long long fwd_ticket = 0;  // the recorded forward's ticket
+  long long n_dir_sums_backwards = 0, n_dir_sums_fallbacks = 0;  // per-gaussian backwards that read the sums / the rows
   gs::SortFork fork;         // side streams for the per-tile sorts of long lists (created when a forward first needs them)
   // the forward's record (gs_common.h: publish_record): pinned host memory the GPU writes and the host polls
   volatile unsigned long long *h_pub = nullptr;
@@ -177,7 +195,7 @@ struct gsplat_context {
     f(c.ids_c, W); f(c.masks_c, W); f(c.n_c_px, W); f(c.tile_useful, W);
     f(c.seg_first, W); f(c.seg_extra, W); f(c.seg_chk, W);
     f(c.fseg_first, W); f(c.fseg_blocks, W); f(c.fseg_gran, W); f(c.fseg_part, W); f(c.fseg_stop, W);
-    f(c.dir_grad, W); f(c.cam_rows, W); f(c.depth_map, W); f(c.seg_chk_d, W); f(c.fseg_part_d, W);
+    f(c.dir_grad, W); f(c.cam_rows, W); f(c.dir_sums, W); f(c.depth_map, W); f(c.seg_chk_d, W); f(c.fseg_part_d, W);
     f(c.depth2_map, W); f(c.seg_chk_q, W); f(c.fseg_part_q, W);
     f(c.f3d_scale, W); f(c.f3d_opacity, W);
     f(c.chunk_first, 0u);  // released, not counted: as before this table

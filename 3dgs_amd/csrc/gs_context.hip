@@ -26,6 +26,7 @@ bool no_compact_lists() { static const bool v = env_is("GSPLAT_NO_COMPACT_LISTS"
 bool no_segments() { static const bool v = env_is("GSPLAT_NO_SEGMENTS", '1'); return v; }
 bool no_fwd_segments() { static const bool v = env_is("GSPLAT_NO_FWD_SEGMENTS", '1'); return v; }
 double fwd_segments_gate() { static const double v = env_number("GSPLAT_FWD_SEGMENTS_GATE", 3.0); return v; }
+bool no_dir_sums() { static const bool v = env_is("GSPLAT_NO_DIR_SUMS", '1'); return v; }
 
 // Room of the instance buffers, in INSTANCES: the smallest element count of the per-instance arrays, minus the one spare
 // slot every user keeps.  Each array is a DeviceBuffer grown by `want + want / 4 + 256` BYTES, so arrays of different
@@ -201,6 +202,12 @@ int gsplat_context_set_compact_lists(gsplat_context *c, int enabled) {
   return GSPLAT_OK;
 }
 
+int gsplat_context_set_dir_sums(gsplat_context *c, int enabled) {
+  GS_REQUIRE(c != nullptr, "null context");
+  c->dir_sums_on = enabled != 0;  // (read by the next forward; a backward follows the forward it belongs to)
+  return GSPLAT_OK;
+}
+
 int gsplat_context_set_absgrad(gsplat_context *c, int enabled) {
   GS_REQUIRE(c != nullptr, "null context");
   c->absgrad = enabled != 0;  // (read by the next compositing backward; the forward has no part in it)
@@ -336,11 +343,11 @@ int gsplat_context_get_counters(gsplat_context *c, long long *out, int n) {
     GS_HIP(hipMemcpy(h.data(), c->tile_useful.ptr, tiles * sizeof(int), hipMemcpyDeviceToHost));
     for (int u : h) useful += u;
   }
-  const long long v[12] = {c->n_forwards, c->n_tail_redone, c->n_compact_walks, c->n_instance_growths, c->n_ordered_backwards,
+  const long long v[14] = {c->n_forwards, c->n_tail_redone, c->n_compact_walks, c->n_instance_growths, c->n_ordered_backwards,
                            (long long)c->n_segmented_backwards, (long long)c->n_segmented_forwards, fmax, fsum, fallbacks,
-                           c->n_compact_backwards, useful};
-  for (int k = 0; k < n && k < 12; ++k) out[k] = v[k];
-  return 12;
+                           c->n_compact_backwards, useful, c->n_dir_sums_backwards, c->n_dir_sums_fallbacks};
+  for (int k = 0; k < n && k < 14; ++k) out[k] = v[k];
+  return 14;
 }
 
 int gsplat_context_set_render_only(gsplat_context *c, int enabled) {

@@ -30,6 +30,7 @@ struct FwdCall {
   bool compact;              // the per-gaussian kernels walk the compacted slots (gs::compact_walk)
   bool beside;               // the colour kernel beside the geometry kernel (pre_split 2)
   bool ro, mid;              // render only; Sigma, J, conic, colour stored for the caller / the stand-alone backward operators
+  bool sums;                 // the per-gaussian kernel also writes the SH direction sums (gs_context.h: dir_sums)
   bool sparse, keys_ok;      // the counting-sort route (else the radix sorts); every depth key an ordinary positive float
   int *bin_table;            // sparse route: the per-workgroup tile histograms
   unsigned long long ticket;  // of the host record and the figure slots
@@ -64,6 +65,7 @@ static int check_forward_args(const gsplat_context *c, const gsplat_gaussians *g
 static int reclaim_outputs(gsplat_context *c, hipStream_t st) {
   c->have_forward = c->lists_ready = c->rows_ready = c->order_ready = c->depth_ready = c->rows_depth = c->rows_abs = false;
   c->depth_inverse_ready = c->depth_moment_ready = false;
+  c->dir_sums_of.ticket = 0;  // nobody's: only the launch of a kernel that writes the sums names a forward again
   gs::pool_unwatch(&c->last_mask);
   c->last_mask = nullptr;  // rank[] and compact_to_global are about to be overwritten
   gs::DeviceBuffer *outs[13];
@@ -110,6 +112,12 @@ static int plan_forward_call(gsplat_context *c, const gsplat_gaussians *g, const
     }
   }
   f.ro = c->render_only; f.mid = !f.ro && !c->lean;
+  // the direction sums: written by the one fused kernel only -- the two-kernel forms and the anti-aliased form have no
+  // such instantiation, and a forward nobody differentiates needs none.  Not at degree 0 either: there is no row to save,
+  // the sums (36 B) are more than the band 0 and xyz_c (24 B) they would replace, and a forward-only caller would pay for
+  // the stores (config2: +0.8 us of 78 with them)
+  f.sums = c->dir_sums_on && !gs::no_dir_sums() && l_max > 0 && !f.ro && c->pre_split == 0 && !c->antialiased;
+  if (f.sums && (rc = c->dir_sums.reserve((size_t)c->max_gaussians * 9 * sizeof(float), st))) return rc;
   // Two binning routes, both exact for any scene; the choice only affects speed, so it follows the LAST forward's
   // density (the first call starts sparse): sparse = LDS counting sort + per-tile depth sort, dense (more than
   // ~768 list entries per tile) or very large tile grids = stable radix sorts (gs_binning.hip).
@@ -199,8 +207,15 @@ static int launch_per_gaussian(gsplat_context *c, FwdCall &f) {
       if (gs::pre_join_late()) f.join_pending = true;
       else GS_HIP(hipStreamWaitEvent(st, c->ev_pre_join, 0));
     }
-  } else if ((rc = gs::launch_preprocess(a, st))) {
-    return rc;
+  } else {
+    if (f.sums) a.dir_sums = c->dir_sums.as<float>();
+    if ((rc = gs::launch_preprocess(a, st))) return rc;
+    if (f.sums) {  // the buffer now holds this forward's sums, of these inputs
+      gsplat_context::DirSumsOf &of = c->dir_sums_of;
+      of.ticket = f.ticket;
+      of.xyz = f.g->xyz; of.rgb = f.g->rgb; of.sh = f.g->sh; of.view = f.cam->view;
+      for (int k = 0; k < 3; ++k) of.campos[k] = f.cam->campos[k];
+    }
   }
   c->fwd_antialiased = c->antialiased;
   return GSPLAT_OK;
@@ -461,6 +476,7 @@ static void record_forward(gsplat_context *c, const FwdCall &f, const gs::Forwar
   gs::pool_watch(c->last_mask, &c->last_mask);  // cleared when whoever ends up owning the block returns it to the pool
   c->tan_fovx = f.tan_fovx; c->tan_fovy = f.tan_fovy; c->mh_dist = f.cfg->mh_dist;
   c->have_forward = !f.ro;  // a render-only forward leaves nothing for a backward
+  c->fwd_ticket = f.ticket;
   c->lists_ready = true;
   c->depth_ready = c->depth;
   c->depth_inverse_ready = c->depth && f.dmap.inverse;
@@ -523,6 +539,7 @@ int gsplat_rasterize_image(gsplat_context *c, const gsplat_gaussians *g, const g
     if ((rc = finish_radix_route(c, f, rec, room))) return rc;
   } else if (gs::tail_needs_redo(rec.S, room, spec_hint, rec.longest, f.keys_ok)) {
     c->n_tail_redone++;
+    c->dir_sums_of.ticket = 0;  // (a forward queued twice: its backwards take the path that reads the rows)
     if (rec.S > room) {  // grow (synchronises); the placement queued below writes the true ranges
       c->n_instance_growths++;
       if ((rc = gs::reserve_instances(c, rec.S + rec.S / 4, f.num_tiles, st))) return rc;
@@ -742,6 +759,21 @@ static int backward_gaussians_impl(const char *fn, gsplat_context *c, const gspl
   if (cam_grad) { a.cam_rows = c->cam_rows.as<double>(); a.grad_view = grad_view; a.grad_campos = grad_campos; }
   a.l_max = l_max; a.rows_depth = c->rows_depth; a.rows_abs = c->rows_abs;
   a.antialiased = c->fwd_antialiased;  // (plain form only: the Adam and camera forms were refused for such a forward above)
+  // The forward's SH direction sums instead of the SH rows: the plain form and adam_mode 1 (the kernel's kAdam 1, which
+  // steps nothing the sums were formed from before it has used them), and only the sums of the forward this call
+  // differentiates, formed from the arrays and the camera this call was given.  (The degree needs no term of its own:
+  // check_recorded_forward has refused any l_max but the recorded forward's, and the ticket says the sums are that forward's.)
+  // An Adam form steps parameters in place, so whatever it read, the sums are nobody's afterwards.
+  {
+    const gsplat_context::DirSumsOf &of = c->dir_sums_of;
+    const bool sums = c->dir_sums_on && !gs::no_dir_sums() && (!adam || adam_mode == 1) && !cam_grad && !a.antialiased && c->dir_sums.ptr != nullptr && of.ticket != 0 &&
+                      of.ticket == c->fwd_ticket && of.xyz == g->xyz && of.rgb == g->rgb &&
+                      of.sh == g->sh && of.view == cam->view && of.campos[0] == cam->campos[0] && of.campos[1] == cam->campos[1] &&
+                      of.campos[2] == cam->campos[2];
+    if (sums) a.dir_sums = c->dir_sums.as<float>();
+    (sums ? c->n_dir_sums_backwards : c->n_dir_sums_fallbacks)++;
+    if (adam) c->dir_sums_of.ticket = 0;
+  }
   if ((rc = gs::launch_preprocess_bwd(a, st))) return rc;
   if (c->fwd_filter3d) {  // d/d (scale_eff, opacity_eff) -> d/d (scale, opacity), in place on the rows just written
     const int lo = whole ? 0 : first_gaussian, hi = whole ? 0 : end_gaussian;

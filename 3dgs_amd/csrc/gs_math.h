@@ -184,60 +184,78 @@ __device__ __forceinline__ void conic_radius(const float *J, const float *s, con
 #define GS_SH_C8 0.3731763325901154f
 #define GS_SH_C9 1.445305721320277f
 
-template <int L>
-__device__ __forceinline__ void sh_basis(float x, float y, float z, float *Y) {
-  Y[0] = GS_SH_C0;
-  if constexpr (L >= 1) {
-    Y[1] = GS_SH_C1 * y; Y[2] = GS_SH_C1 * z; Y[3] = GS_SH_C1 * x;
-  }
-  if constexpr (L >= 2) {
+// One band at a time -- Y[m], m = 0 .. 2B, is entry B*B + m of the whole table -- so that a caller can form a band where it
+// uses it (sh_to_rgb_dir_sums).
+template <int B>
+__device__ __forceinline__ void sh_basis_band(float x, float y, float z, float *Y) {
+  static_assert(B >= 0 && B <= 3, "bands 0..3");
+  if constexpr (B == 0) {
+    Y[0] = GS_SH_C0;
+  } else if constexpr (B == 1) {
+    Y[0] = GS_SH_C1 * y; Y[1] = GS_SH_C1 * z; Y[2] = GS_SH_C1 * x;
+  } else if constexpr (B == 2) {
     const float xx = x * x, yy = y * y, zz = z * z;
-    Y[4] = GS_SH_C2 * (x * y);
-    Y[5] = GS_SH_C2 * (y * z);
-    Y[6] = GS_SH_C3 * (2.0f * zz - xx - yy);
-    Y[7] = GS_SH_C2 * (x * z);
-    Y[8] = GS_SH_C4 * (xx - yy);
-    if constexpr (L >= 3) {
-      Y[9] = GS_SH_C5 * (y * (3.0f * xx - yy));
-      Y[10] = GS_SH_C6 * (x * y * z);
-      Y[11] = GS_SH_C7 * (y * (4.0f * zz - xx - yy));
-      Y[12] = GS_SH_C8 * (z * (2.0f * zz - 3.0f * xx - 3.0f * yy));
-      Y[13] = GS_SH_C7 * (x * (4.0f * zz - xx - yy));
-      Y[14] = GS_SH_C9 * (z * (xx - yy));
-      Y[15] = GS_SH_C5 * (x * (xx - 3.0f * yy));
-    }
+    Y[0] = GS_SH_C2 * (x * y);
+    Y[1] = GS_SH_C2 * (y * z);
+    Y[2] = GS_SH_C3 * (2.0f * zz - xx - yy);
+    Y[3] = GS_SH_C2 * (x * z);
+    Y[4] = GS_SH_C4 * (xx - yy);
+  } else {
+    const float xx = x * x, yy = y * y, zz = z * z;
+    Y[0] = GS_SH_C5 * (y * (3.0f * xx - yy));
+    Y[1] = GS_SH_C6 * (x * y * z);
+    Y[2] = GS_SH_C7 * (y * (4.0f * zz - xx - yy));
+    Y[3] = GS_SH_C8 * (z * (2.0f * zz - 3.0f * xx - 3.0f * yy));
+    Y[4] = GS_SH_C7 * (x * (4.0f * zz - xx - yy));
+    Y[5] = GS_SH_C9 * (z * (xx - yy));
+    Y[6] = GS_SH_C5 * (x * (xx - 3.0f * yy));
   }
 }
+template <int L>
+__device__ __forceinline__ void sh_basis(float x, float y, float z, float *Y) {
+  sh_basis_band<0>(x, y, z, Y);
+  if constexpr (L >= 1) sh_basis_band<1>(x, y, z, Y + 1);
+  if constexpr (L >= 2) sh_basis_band<2>(x, y, z, Y + 4);
+  if constexpr (L >= 3) sh_basis_band<3>(x, y, z, Y + 9);
+}
 
-// Cartesian gradient of the same polynomials: d[k] = (dY_k/dx, dY_k/dy, dY_k/dz)
+// Cartesian gradient of the same polynomials: d[k] = (dY_k/dx, dY_k/dy, dY_k/dz).  One band at a time -- d[m], m = 0 .. 2B,
+// is entry B*B + m of the whole table -- so that a caller can form a band where it uses it (sh_dir_sums).
+template <int B>
+__device__ __forceinline__ void sh_basis_grad_band(float x, float y, float z, float (*d)[3]) {
+  static_assert(B >= 0 && B <= 3, "bands 0..3");
+  if constexpr (B == 0) {
+    d[0][0] = d[0][1] = d[0][2] = 0.0f;
+  } else if constexpr (B == 1) {
+    d[0][0] = 0; d[0][1] = GS_SH_C1; d[0][2] = 0;
+    d[1][0] = 0; d[1][1] = 0; d[1][2] = GS_SH_C1;
+    d[2][0] = GS_SH_C1; d[2][1] = 0; d[2][2] = 0;
+  } else if constexpr (B == 2) {
+    d[0][0] = GS_SH_C2 * y; d[0][1] = GS_SH_C2 * x; d[0][2] = 0;
+    d[1][0] = 0; d[1][1] = GS_SH_C2 * z; d[1][2] = GS_SH_C2 * y;
+    d[2][0] = GS_SH_C3 * (-2.0f * x); d[2][1] = GS_SH_C3 * (-2.0f * y); d[2][2] = GS_SH_C3 * (4.0f * z);
+    d[3][0] = GS_SH_C2 * z; d[3][1] = 0; d[3][2] = GS_SH_C2 * x;
+    d[4][0] = GS_SH_C4 * (2.0f * x); d[4][1] = GS_SH_C4 * (-2.0f * y); d[4][2] = 0;
+  } else {
+    const float xx = x * x, yy = y * y, zz = z * z;
+    d[0][0] = GS_SH_C5 * (6.0f * x * y); d[0][1] = GS_SH_C5 * (3.0f * xx - 3.0f * yy); d[0][2] = 0;
+    d[1][0] = GS_SH_C6 * (y * z); d[1][1] = GS_SH_C6 * (x * z); d[1][2] = GS_SH_C6 * (x * y);
+    d[2][0] = GS_SH_C7 * (-2.0f * x * y); d[2][1] = GS_SH_C7 * (4.0f * zz - xx - 3.0f * yy);
+    d[2][2] = GS_SH_C7 * (8.0f * y * z);
+    d[3][0] = GS_SH_C8 * (-6.0f * x * z); d[3][1] = GS_SH_C8 * (-6.0f * y * z);
+    d[3][2] = GS_SH_C8 * (6.0f * zz - 3.0f * xx - 3.0f * yy);
+    d[4][0] = GS_SH_C7 * (4.0f * zz - 3.0f * xx - yy); d[4][1] = GS_SH_C7 * (-2.0f * x * y);
+    d[4][2] = GS_SH_C7 * (8.0f * x * z);
+    d[5][0] = GS_SH_C9 * (2.0f * x * z); d[5][1] = GS_SH_C9 * (-2.0f * y * z); d[5][2] = GS_SH_C9 * (xx - yy);
+    d[6][0] = GS_SH_C5 * (3.0f * xx - 3.0f * yy); d[6][1] = GS_SH_C5 * (-6.0f * x * y); d[6][2] = 0;
+  }
+}
 template <int L>
 __device__ __forceinline__ void sh_basis_grad(float x, float y, float z, float (*d)[3]) {
-  d[0][0] = d[0][1] = d[0][2] = 0.0f;
-  if constexpr (L >= 1) {
-    d[1][0] = 0; d[1][1] = GS_SH_C1; d[1][2] = 0;
-    d[2][0] = 0; d[2][1] = 0; d[2][2] = GS_SH_C1;
-    d[3][0] = GS_SH_C1; d[3][1] = 0; d[3][2] = 0;
-  }
-  if constexpr (L >= 2) {
-    const float xx = x * x, yy = y * y, zz = z * z;
-    d[4][0] = GS_SH_C2 * y; d[4][1] = GS_SH_C2 * x; d[4][2] = 0;
-    d[5][0] = 0; d[5][1] = GS_SH_C2 * z; d[5][2] = GS_SH_C2 * y;
-    d[6][0] = GS_SH_C3 * (-2.0f * x); d[6][1] = GS_SH_C3 * (-2.0f * y); d[6][2] = GS_SH_C3 * (4.0f * z);
-    d[7][0] = GS_SH_C2 * z; d[7][1] = 0; d[7][2] = GS_SH_C2 * x;
-    d[8][0] = GS_SH_C4 * (2.0f * x); d[8][1] = GS_SH_C4 * (-2.0f * y); d[8][2] = 0;
-    if constexpr (L >= 3) {
-      d[9][0] = GS_SH_C5 * (6.0f * x * y); d[9][1] = GS_SH_C5 * (3.0f * xx - 3.0f * yy); d[9][2] = 0;
-      d[10][0] = GS_SH_C6 * (y * z); d[10][1] = GS_SH_C6 * (x * z); d[10][2] = GS_SH_C6 * (x * y);
-      d[11][0] = GS_SH_C7 * (-2.0f * x * y); d[11][1] = GS_SH_C7 * (4.0f * zz - xx - 3.0f * yy);
-      d[11][2] = GS_SH_C7 * (8.0f * y * z);
-      d[12][0] = GS_SH_C8 * (-6.0f * x * z); d[12][1] = GS_SH_C8 * (-6.0f * y * z);
-      d[12][2] = GS_SH_C8 * (6.0f * zz - 3.0f * xx - 3.0f * yy);
-      d[13][0] = GS_SH_C7 * (4.0f * zz - 3.0f * xx - yy); d[13][1] = GS_SH_C7 * (-2.0f * x * y);
-      d[13][2] = GS_SH_C7 * (8.0f * x * z);
-      d[14][0] = GS_SH_C9 * (2.0f * x * z); d[14][1] = GS_SH_C9 * (-2.0f * y * z); d[14][2] = GS_SH_C9 * (xx - yy);
-      d[15][0] = GS_SH_C5 * (3.0f * xx - 3.0f * yy); d[15][1] = GS_SH_C5 * (-6.0f * x * y); d[15][2] = 0;
-    }
-  }
+  sh_basis_grad_band<0>(x, y, z, d);
+  if constexpr (L >= 1) sh_basis_grad_band<1>(x, y, z, d + 1);
+  if constexpr (L >= 2) sh_basis_grad_band<2>(x, y, z, d + 4);
+  if constexpr (L >= 3) sh_basis_grad_band<3>(x, y, z, d + 9);
 }
 
 // view direction (reference: compute_dir_kernel, cuda/spherical_harmonics.cu:8-26)
@@ -564,6 +582,119 @@ __device__ __forceinline__ void sigma_bwd(const RotScale &rs, const float *g /*6
   dQ[3] = rs.inv_norm * (dz - dot * z);
 }
 
+// ---- S2's two halves: sh_bwd (below) split, so that the nine sums over the coefficient row can be formed where the row is in registers anyway
+// (preprocess_kernel<.., kDirSums>) and finished where the colour gradient exists (preprocess_bwd_kernel<.., kDirSums>).
+// sh_dir_sums: s[3 * axis + channel] = sum_k dY_k/d(axis)(u) * coefficient[k][channel] at the unit direction u, left to
+// right: 0, the band-0 term, then k = 0 .. n - 2 -- sh_bwd's dRx dGx dBx | dRy .. | dRz ...  `each_k(k)` runs once per
+// coefficient, after it has been read and before its products are added (sh_bwd stores the coefficient's gradient there,
+// possibly over the coefficient itself).
+// TWO bodies, one arithmetic: the default forms the basis gradient as one table in front and is sh_bwd's loop as it always
+// was (the rows path keeps its code); kLazy is what the forward runs.  They share sh_basis_grad_band's expressions and add
+// the same products in the same order, but they are two texts: that their sums are the same bits is what
+// tests/test_dir_sums_gpu.py checks, word for word, not something the sharing of code guarantees.
+// kLazy: the basis gradient is formed band by band, behind each_k of the band's first coefficient, instead of as one
+// 16 x 3 table in front -- the same expressions, hence the same sums -- and the hook is each_k(k, ux, uy, uz, s) with the
+// direction the band will be formed from and the sums so far, all by reference: a caller short of registers
+// (preprocess_kernel) ties them together there, so that a band's table cannot exist before the band in front is summed.
+template <int B, class F>
+__device__ __forceinline__ void sh_dir_sums_band(const float *sh, float ux, float uy, float uz, float *s /*9*/, F &&each_k) {
+  constexpr int k0 = B * B - 1, nb = 2 * B + 1;  // the band's first coefficient of the row, and how many it has
+  float d[nb][3];
+#pragma unroll
+  for (int m = 0; m < nb; ++m) {
+    const int k = k0 + m;
+    const float Ri = sh[3 * k], Gi = sh[3 * k + 1], Bi = sh[3 * k + 2];
+    each_k(k, ux, uy, uz, s);
+    if (m == 0) sh_basis_grad_band<B>(ux, uy, uz, d);
+    const float ddx = d[m][0], ddy = d[m][1], ddz = d[m][2];
+    s[0] += ddx * Ri; s[1] += ddx * Gi; s[2] += ddx * Bi;
+    s[3] += ddy * Ri; s[4] += ddy * Gi; s[5] += ddy * Bi;
+    s[6] += ddz * Ri; s[7] += ddz * Gi; s[8] += ddz * Bi;
+  }
+}
+template <int L, bool kLazy = false, class F>
+__device__ __forceinline__ void sh_dir_sums(const float *sh, const float *__restrict__ band0, float ux, float uy, float uz,
+                                            float *s /*9*/, F &&each_k) {
+  constexpr int n = (L + 1) * (L + 1);
+  if constexpr (kLazy) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = 0;
+    {
+      float d0[1][3];
+      sh_basis_grad_band<0>(ux, uy, uz, d0);
+      const float R0 = band0[0], G0 = band0[1], B0 = band0[2];
+      s[0] += d0[0][0] * R0; s[1] += d0[0][0] * G0; s[2] += d0[0][0] * B0;
+      s[3] += d0[0][1] * R0; s[4] += d0[0][1] * G0; s[5] += d0[0][1] * B0;
+      s[6] += d0[0][2] * R0; s[7] += d0[0][2] * G0; s[8] += d0[0][2] * B0;
+    }
+    if constexpr (L >= 1) sh_dir_sums_band<1>(sh, ux, uy, uz, s, each_k);
+    if constexpr (L >= 2) sh_dir_sums_band<2>(sh, ux, uy, uz, s, each_k);
+    if constexpr (L >= 3) sh_dir_sums_band<3>(sh, ux, uy, uz, s, each_k);
+  } else {
+    float dY[n][3];
+    sh_basis_grad<L>(ux, uy, uz, dY);
+    float dRx = 0, dGx = 0, dBx = 0, dRy = 0, dGy = 0, dBy = 0, dRz = 0, dGz = 0, dBz = 0;
+    {
+      const float R0 = band0[0], G0 = band0[1], B0 = band0[2];
+      dRx += dY[0][0] * R0; dGx += dY[0][0] * G0; dBx += dY[0][0] * B0;
+      dRy += dY[0][1] * R0; dGy += dY[0][1] * G0; dBy += dY[0][1] * B0;
+      dRz += dY[0][2] * R0; dGz += dY[0][2] * G0; dBz += dY[0][2] * B0;
+    }
+#pragma unroll
+    for (int k = 0; k < n - 1; ++k) {
+      const float Ri = sh[3 * k], Gi = sh[3 * k + 1], Bi = sh[3 * k + 2];
+      each_k(k);
+      const float ddx = dY[k + 1][0], ddy = dY[k + 1][1], ddz = dY[k + 1][2];
+      dRx += ddx * Ri; dGx += ddx * Gi; dBx += ddx * Bi;
+      dRy += ddy * Ri; dGy += ddy * Gi; dBy += ddy * Bi;
+      dRz += ddz * Ri; dGz += ddz * Gi; dBz += ddz * Bi;
+    }
+    s[0] = dRx; s[1] = dGx; s[2] = dBx; s[3] = dRy; s[4] = dGy; s[5] = dBy; s[6] = dRz; s[7] = dGz; s[8] = dBz;
+  }
+}
+template <int L>
+__device__ __forceinline__ void sh_dir_sums(const float *sh, const float *__restrict__ band0, float ux, float uy, float uz,
+                                            float *s /*9*/) {
+  sh_dir_sums<L>(sh, band0, ux, uy, uz, s, [](int) {});
+}
+
+// sh_to_rgb and sh_dir_sums in ONE walk over the row (preprocess_kernel<.., kDirSums>): coefficient k enters the colour --
+// sh_to_rgb's statements, in its order -- and then the nine sums, so a coefficient is dead after its twelve products, and a
+// band of the basis and of its gradient exists only while the band is walked.  `pin(x, y, z, s, r, g, b)` runs in front of
+// every band's first coefficient and in the middle of bands 2 and 3, with the direction, the sums and the colour so far, by
+// reference: the kernel passes them through an empty asm there, which makes what follows depend on what is in front being
+// finished (the values are untouched).
+template <int L, class F>
+__device__ __forceinline__ void sh_to_rgb_dir_sums(const float *sh, const float *__restrict__ band0, float dx, float dy,
+                                                   float dz, float *rgb, float *s /*9*/, F &&pin) {
+  float Y[16];  // (whole table's size at every degree: the hook below names every band; only the walked ones are formed)
+  sh_basis_band<0>(dx, dy, dz, Y);
+  float r = band0[0] * Y[0] + 0.5f, g = band0[1] * Y[0] + 0.5f, b = band0[2] * Y[0] + 0.5f;
+  sh_dir_sums<L, true>(sh, band0, dx, dy, dz, s, [&](int k, float &x, float &y, float &z, float *acc) {
+    if (k == 0 || k == 3 || k == 5 || k == 8 || k == 11) pin(x, y, z, acc, r, g, b);
+    if (k == 0) sh_basis_band<1>(x, y, z, Y + 1);
+    if (k == 3) sh_basis_band<2>(x, y, z, Y + 4);
+    if (k == 8) sh_basis_band<3>(x, y, z, Y + 9);
+    r += sh[3 * k + 0] * Y[k + 1];
+    g += sh[3 * k + 1] * Y[k + 1];
+    b += sh[3 * k + 2] * Y[k + 1];
+  });
+  rgb[0] = r; rgb[1] = g; rgb[2] = b;
+}
+
+// ... and from the nine sums to the position gradient through the view direction: the colour gradient's weights, the part
+// orthogonal to u, the division by the distance (view_dir's len)
+__device__ __forceinline__ void sh_dir_finish(const float *s /*9*/, const float *gr, float ux, float uy, float uz, float len,
+                                              float &ox, float &oy, float &oz) {
+  const float tx = gr[0] * s[0] + gr[1] * s[1] + gr[2] * s[2];
+  const float ty = gr[0] * s[3] + gr[1] * s[4] + gr[2] * s[5];
+  const float tz = gr[0] * s[6] + gr[1] * s[7] + gr[2] * s[8];
+  const float dot = tx * ux + ty * uy + tz * uz;
+  ox = (tx - dot * ux) / len;
+  oy = (ty - dot * uy) / len;
+  oz = (tz - dot * uz) / len;
+}
+
 // ---- S2 (reference: compute_sh_gradients_kernel, cuda/spherical_harmonics_backward.cu:28-166)
 // Writes sh_grad (n-1)*3 and band0_grad 3 (overwrite), returns the xyz increment.
 // kStoreGrad = false (r06, the backward that applies Adam itself): the coefficient gradients are not stored -- their
@@ -578,34 +709,14 @@ __device__ __forceinline__ void sh_bwd(const float *sh, const float *__restrict_
   float ux, uy, uz, len;
   view_dir(px, py, pz, cx, cy, cz, ux, uy, uz, len);
   float Y[n];
-  float dY[n][3];
   sh_basis<L>(ux, uy, uz, Y);
-  sh_basis_grad<L>(ux, uy, uz, dY);
   band0_grad[0] = gr[0] * Y[0]; band0_grad[1] = gr[1] * Y[0]; band0_grad[2] = gr[2] * Y[0];
-  float dRx = 0, dGx = 0, dBx = 0, dRy = 0, dGy = 0, dBy = 0, dRz = 0, dGz = 0, dBz = 0;
-  {
-    const float R0 = band0[0], G0 = band0[1], B0 = band0[2];
-    dRx += dY[0][0] * R0; dGx += dY[0][0] * G0; dBx += dY[0][0] * B0;
-    dRy += dY[0][1] * R0; dGy += dY[0][1] * G0; dBy += dY[0][1] * B0;
-    dRz += dY[0][2] * R0; dGz += dY[0][2] * G0; dBz += dY[0][2] * B0;
-  }
-#pragma unroll
-  for (int k = 0; k < n - 1; ++k) {
+  float s[9];
+  sh_dir_sums<L>(sh, band0, ux, uy, uz, s, [&](int k) {
     const float yv = Y[k + 1];
-    const float Ri = sh[3 * k], Gi = sh[3 * k + 1], Bi = sh[3 * k + 2];
     if constexpr (kStoreGrad) { sh_grad[3 * k] = gr[0] * yv; sh_grad[3 * k + 1] = gr[1] * yv; sh_grad[3 * k + 2] = gr[2] * yv; }
-    const float ddx = dY[k + 1][0], ddy = dY[k + 1][1], ddz = dY[k + 1][2];
-    dRx += ddx * Ri; dGx += ddx * Gi; dBx += ddx * Bi;
-    dRy += ddy * Ri; dGy += ddy * Gi; dBy += ddy * Bi;
-    dRz += ddz * Ri; dGz += ddz * Gi; dBz += ddz * Bi;
-  }
-  const float tx = gr[0] * dRx + gr[1] * dGx + gr[2] * dBx;
-  const float ty = gr[0] * dRy + gr[1] * dGy + gr[2] * dBy;
-  const float tz = gr[0] * dRz + gr[1] * dGz + gr[2] * dBz;
-  const float dot = tx * ux + ty * uy + tz * uz;
-  ox = (tx - dot * ux) / len;
-  oy = (ty - dot * uy) / len;
-  oz = (tz - dot * uz) / len;
+  });
+  sh_dir_finish(s, gr, ux, uy, uz, len, ox, oy, oz);
 }
 
 // ---- f2: one element of the reference's adam_kernel (cuda/optimizer.cu:6-29): NaN gradients count as 0, bias-corrected

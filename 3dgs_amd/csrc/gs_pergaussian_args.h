@@ -37,6 +37,7 @@ struct PreprocessArgs {
   int *counts;
   unsigned long long *hitmask, *pairs;
   int *table;  // counting-sort route: the per-workgroup tile histograms (the launcher sizes the LDS one); else null
+  float *dir_sums;  // launch_preprocess only: [M,9] gs::sh_dir_sums per kept gaussian (preprocess_kernel<.., kDirSums>); else null
   // the form
   int l_max;         // launch_preprocess only
   bool store_mid;    // Sigma, J, conic and colour are stored
@@ -74,6 +75,9 @@ struct PreprocessBwdArgs {
   float *adam_dir;                // adam_mode 3: [M,3], from sh_adam_dir_kernel
   double *cam_rows;               // camera form: [ceil(span/64),16] partial sums ...
   float *grad_view, *grad_campos;  // ... and where cam_grad_finalize_kernel leaves their totals
+  // plain form and adam_mode 1 (no other Adam form, no camera or anti-aliased form): [M,9] the recorded forward's gs::sh_dir_sums, read INSTEAD of the SH
+  // rows, band 0 and xyz_c (preprocess_bwd_kernel<.., kDirSums>); null: the kernel reads the rows
+  const float *dir_sums;
   // the form
   int l_max;
   int adam_mode;  // 0 none; the kernel's kAdam 1, 2, 3

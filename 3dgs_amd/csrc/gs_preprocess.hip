@@ -123,6 +123,7 @@ struct PreOut {
   int *counts;
   unsigned long long *hitmask;  // per gaussian: one bit per tile of its coarse rectangle (rectangles of <= 64 tiles)
   unsigned long long *pairs;  // 64 spread counters of coarse candidate pairs (reporting only)
+  float *dir_sums;  // kDirSums: [M,9] gs::sh_dir_sums of every kept gaussian, for the per-gaussian backward
 };
 
 // ---- B: everything per kept gaussian, written at its compacted slot
@@ -140,7 +141,12 @@ struct PreOut {
 // Sigma, J, conic, colour and the 48-byte record pushed the SH-3 instance past its 128 registers (6 spilled in r02).
 //   kAntialias (gsplat_context_set_antialiased): the record's opacity is sigmoid(logit) * rho; conic, radii and tile tests
 //     are what they are without the flag -- a template flag, so that the default instantiations stay exactly what they were
-template <int L, bool kStoreMid, bool kCompact, bool kAntialias = false>
+//   kDirSums (gsplat_context_set_dir_sums): the lane also forms gs::sh_dir_sums -- the nine sums over its coefficient row
+//     that the position gradient through the view direction is made of -- while the row is in its registers for the colour,
+//     and stores them at its compacted slot (36 bytes); preprocess_bwd_kernel<.., kDirSums> then reads those instead of the
+//     row, band 0 and the camera-space position (204 bytes).  The sums are gs::sh_bwd's own, the same inlined code on the same
+//     inputs.  Again a template flag: every other instantiation is what it was.
+template <int L, bool kStoreMid, bool kCompact, bool kAntialias = false, bool kDirSums = false>
 __global__ __launch_bounds__(gs::kBinThreads) void preprocess_kernel(gsplat_gaussians g, const float *__restrict__ view,
                                                             const unsigned char *__restrict__ mask,
                                                             int *__restrict__ rank,
@@ -226,7 +232,32 @@ __global__ __launch_bounds__(gs::kBinThreads) void preprocess_kernel(gsplat_gaus
     // colour
     float dx, dy, dz, len, rgb[3];
     gs::view_dir(g.xyz[3 * i], g.xyz[3 * i + 1], g.xyz[3 * i + 2], cx, cy, cz, dx, dy, dz, len);
-    gs::sh_to_rgb<L>(g.sh + (size_t)i * (n - 1) * 3, g.rgb + 3 * i, dx, dy, dz, rgb);
+    if constexpr (kDirSums) {
+      // The row and band 0 are loaded ONCE, into registers, and walked once for the colour and the sums.  Left to itself
+      // the compiler forms the whole basis and all of its gradient while the 45 coefficients are in flight, next to twelve
+      // accumulators, and the degree-3 kernels spill (10 to 69 registers, every form tried); scheduling barriers do not
+      // hold arithmetic in place.  So the walk is tied together by data: at five points the direction and the running
+      // sums pass through one empty asm, and nothing behind it can be formed before everything in front of it is summed.
+      // Degree 3: 114 to 120 registers, no scratch (the kernel without the flag: 127 / 128).
+      constexpr int kRow = (n - 1) * 3;
+      float row[kRow > 0 ? kRow : 1], b0[3];
+      {
+        const float *src = g.sh + (size_t)i * kRow;
+#pragma unroll
+        for (int k = 0; k < kRow; ++k) row[k] = src[k];
+        b0[0] = g.rgb[3 * i]; b0[1] = g.rgb[3 * i + 1]; b0[2] = g.rgb[3 * i + 2];
+      }
+      float ds[9];
+      gs::sh_to_rgb_dir_sums<L>(row, b0, dx, dy, dz, rgb, ds, [](float &x, float &y, float &z, float *s, float &r, float &g, float &b) {
+        asm volatile("" : "+v"(x), "+v"(y), "+v"(z), "+v"(s[0]), "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]),
+                          "+v"(s[6]), "+v"(s[7]), "+v"(s[8]), "+v"(r), "+v"(g), "+v"(b));
+      });
+      float *dst = o.dir_sums + 9 * (size_t)j;  // (stored at once: nine registers that nothing below needs)
+#pragma unroll
+      for (int k = 0; k < 9; ++k) dst[k] = ds[k];
+    } else {
+      gs::sh_to_rgb<L>(g.sh + (size_t)i * (n - 1) * 3, g.rgb + 3 * i, dx, dy, dz, rgb);
+    }
     // covariance -> conic
     const float4 q = reinterpret_cast<const float4 *>(g.quaternion)[i];
     const gs::RotScale rs = gs::rot_scale(q.x, q.y, q.z, q.w, g.scale[3 * i], g.scale[3 * i + 1], g.scale[3 * i + 2]);
@@ -766,7 +797,8 @@ int launch_project_cull(const CullArgs &a, hipStream_t st) {
 // kBinThreads, the tile histogram (counting-sort route) as dynamic LDS
 template <class Kernel>
 static void launch_per_gaussian(Kernel kernel, const PreprocessArgs &a, hipStream_t st) {
-  const PreOut o = {a.c2g, a.xyz_c, a.uv, a.sigma, a.conic, a.J, a.rgb, a.radius, a.recs, a.counts, a.hitmask, a.pairs};
+  const PreOut o = {a.c2g, a.xyz_c, a.uv, a.sigma, a.conic, a.J, a.rgb, a.radius, a.recs, a.counts, a.hitmask, a.pairs,
+                    a.dir_sums};
   const size_t hist_bytes = a.table ? (size_t)a.ntx * a.nty * sizeof(int) : 0;
   kernel<<<kBinBlocks, kBinThreads, hist_bytes, st>>>(a.g, a.view, a.mask, a.rank, a.slice_counts, a.kept, a.proj, a.width,
                                                       a.height, a.fx, a.fy, a.tan_fovx, a.tan_fovy, a.mh_dist, a.campos[0],
@@ -774,12 +806,15 @@ static void launch_per_gaussian(Kernel kernel, const PreprocessArgs &a, hipStrea
 }
 
 int launch_preprocess(const PreprocessArgs &a, hipStream_t st) {
+  GS_REQUIRE(!(a.antialiased && a.dir_sums), "the anti-aliased forward has no form that writes the direction sums");
   with_degree<0>(a.l_max, [&](auto L) {
     with_bool(a.store_mid, [&](auto mid) {
       with_bool(a.compact, [&](auto cmp) {
-        with_bool(a.antialiased, [&](auto aa) {
-          launch_per_gaussian(preprocess_kernel<decltype(L)::value, decltype(mid)::value, decltype(cmp)::value, decltype(aa)::value>, a, st);
-        });
+        constexpr int kL = decltype(L)::value;
+        constexpr bool kMid = decltype(mid)::value, kCmp = decltype(cmp)::value;
+        if (a.antialiased) launch_per_gaussian(preprocess_kernel<kL, kMid, kCmp, true>, a, st);
+        else if (a.dir_sums) launch_per_gaussian(preprocess_kernel<kL, kMid, kCmp, false, true>, a, st);
+        else launch_per_gaussian(preprocess_kernel<kL, kMid, kCmp, false>, a, st);
       });
     });
   });

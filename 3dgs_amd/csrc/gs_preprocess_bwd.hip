@@ -93,7 +93,16 @@ struct AdamFused {
 // for bit its value, like Sigma, J and the conic); g_eff becomes dL/d logit and dL/d rho (gs::effective_opacity_bwd), and
 // dL/d rho enters conic_bwd as a covariance term (gs::compensation_bwd) -- dJ, dSigma and everything behind them take it
 // through the code that is there.
-template <int L, int kAdam = 0, bool kDepthRow = false, bool kCamGrad = false, bool kAbsRow = false, bool kAntialias = false>
+// kDirSums (the plain form and kAdam 1; gsplat_context_set_dir_sums): the recorded forward left gs::sh_dir_sums of every kept gaussian
+// in dir_sums [M,9] (preprocess_kernel<.., kDirSums>).  The coefficient rows, band 0 and xyz_c are then not read at all:
+// the coefficient gradients g_rgb[c] * Y_k need no coefficient, the position gradient through the view direction is
+// gs::sh_dir_finish of the nine loaded sums, and the camera-space position is gs::camera_space of the position this kernel
+// loads anyway -- the forward's function on the forward's inputs, bit for bit what it stored.  204 bytes per gaussian
+// become 36; every result is the bits of the form without the flag.  kAdam 1 (the trainer's default iteration) stores no
+// coefficient gradients, so with the flag it touches neither the rows nor the LDS: its SH group is stepped by
+// gsplat_optimizer_step_sh_factored behind it, which reads the rows for the update it makes.
+template <int L, int kAdam = 0, bool kDepthRow = false, bool kCamGrad = false, bool kAbsRow = false, bool kAntialias = false,
+          bool kDirSums = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam == 3 ? GS_BWD3_WAVES : 3, 8))) void preprocess_bwd_kernel(gsplat_gaussians g, const float *__restrict__ view,
                                                                 const float *__restrict__ proj, int M,
                                                                 const int *__restrict__ c2g,
@@ -103,7 +112,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
                                                                 float fwd_tan_fovy, float mh_dist, float cx, float cy,
                                                                 float cz, int width, int height, BwdOut o,
                                                                 int ranged, int i_lo, int i_hi, AdamFused ad,
-                                                                double *__restrict__ cam_rows) {
+                                                                double *__restrict__ cam_rows,
+                                                                const float *__restrict__ dir_sums) {
+  static_assert(!kDirSums || ((kAdam == 0 || kAdam == 1) && !kCamGrad && !kAntialias),
+                "the direction sums are read by the plain form and by kAdam 1 only");
   static_assert(!kCamGrad || kAdam == 0, "the camera gradient is a form of the plain backward");
   static_assert(!(kCamGrad && kAbsRow), "the camera form stores no densification statistic");
   static_assert(!kAntialias || (kAdam == 0 && !kCamGrad), "anti-aliased mode is a form of the plain backward");
@@ -123,7 +135,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
   // The SH rows (kRest floats per gaussian, 180 B at degree 3) go through LDS: a lane reading ITS row touches 64
   // different cache lines per wave instruction; the wave's 64 rows as one linear span touch 8.  Same for the
   // gradient rows on the way out.  Each wave stages only its own rows (no workgroup barrier).
-  __shared__ __attribute__((aligned(16))) float s_sh[kRest > 0 && kAdam != 3 ? kBlock * kRest : 4];
+  __shared__ __attribute__((aligned(16))) float s_sh[kRest > 0 && kAdam != 3 && !(kDirSums && kAdam != 0) ? kBlock * kRest : 4];
   // kAdam: per row the unit direction and the colour gradient (what the SH gradients are made of) and the global row
   __shared__ float s_dir[kAdam == 2 && kRest > 0 ? kBlock * 7 : 1];
   const int lane = threadIdx.x & 63, wave_first = threadIdx.x - lane;
@@ -132,8 +144,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
   const int rows = min(64, M - jw);
   const bool live = j < M;
   const int i = c2g[live ? j : jw];
-  float *wsh = s_sh + (kAdam != 3 ? wave_first * kRest : 0);
-  if constexpr (kRest > 0 && kAdam != 3) {
+  float *wsh = s_sh + (kAdam != 3 && !(kDirSums && kAdam != 0) ? wave_first * kRest : 0);
+  if constexpr (kRest > 0 && kAdam != 3 && !kDirSums) {
     const int i0 = __builtin_amdgcn_readfirstlane(i);
     if (__all(!live || i == i0 + lane)) {  // consecutive gaussians (no culling in between): one linear span
       gs::rows_to_lds<kRest>(g.sh + (size_t)i0 * kRest, wsh, rows, lane);
@@ -271,6 +283,25 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
     // gradient through the view direction is what sh_adam_dir_kernel left (the same sums in the same order)
     b0g[0] = g_rgb[0] * GS_SH_C0; b0g[1] = g_rgb[1] * GS_SH_C0; b0g[2] = g_rgb[2] * GS_SH_C0;
     gx = ad.dir[3 * (size_t)jr]; gy = ad.dir[3 * (size_t)jr + 1]; gz = ad.dir[3 * (size_t)jr + 2];
+  } else if constexpr (kDirSums) {
+    // gs::sh_bwd without the row: its direction, its gradient expressions, and its last lines on the forward's sums
+    float s[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s[k] = dir_sums[9 * (size_t)jr + k];
+    float ux, uy, uz, len;
+    gs::view_dir(g.xyz[3 * i], g.xyz[3 * i + 1], g.xyz[3 * i + 2], cx, cy, cz, ux, uy, uz, len);
+    float Y[n];
+    gs::sh_basis<L>(ux, uy, uz, Y);
+    b0g[0] = g_rgb[0] * Y[0]; b0g[1] = g_rgb[1] * Y[0]; b0g[2] = g_rgb[2] * Y[0];
+    if constexpr (kAdam == 0) {  // (kAdam 1 stores no coefficient gradients: sh_bwd<L, false>)
+      [[maybe_unused]] float *row = wsh + lane * kRest;
+#pragma unroll
+      for (int k = 0; k < n - 1; ++k) {
+        const float yv = Y[k + 1];
+        row[3 * k] = g_rgb[0] * yv; row[3 * k + 1] = g_rgb[1] * yv; row[3 * k + 2] = g_rgb[2] * yv;
+      }
+    }
+    gs::sh_dir_finish(s, g_rgb, ux, uy, uz, len, gx, gy, gz);
   } else {
     float *row = wsh + lane * kRest;  // read as coefficients, overwritten with their gradients (kAdam: left as they are)
     gs::sh_bwd<L, kAdam == 0>(row, g.rgb + 3 * i, g.xyz[3 * i], g.xyz[3 * i + 1], g.xyz[3 * i + 2], cx, cy, cz, g_rgb, row, b0g,
@@ -312,7 +343,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kAdam ==
   // camera-space position) with the forward's functions and the forward's tan(fov): bit for bit the values
   // preprocess_kernel stored, without reading 60 bytes per gaussian back (the kernel is HBM bound).
   const int jc = kCamGrad ? jr : j;
-  const float x = xyz_c_sel[3 * jc], y = xyz_c_sel[3 * jc + 1], z = xyz_c_sel[3 * jc + 2];
+  float x, y, z;
+  if constexpr (kDirSums) {
+    gs::camera_space(vw, g.xyz[3 * i], g.xyz[3 * i + 1], g.xyz[3 * i + 2], x, y, z);  // (as preprocess_kernel formed it)
+  } else {
+    x = xyz_c_sel[3 * jc]; y = xyz_c_sel[3 * jc + 1]; z = xyz_c_sel[3 * jc + 2];
+  }
   float Jv[6], sg[6], con[3], rad_unused[4], dJ[6], dS[6];
   {
     const float4 q = reinterpret_cast<const float4 *>(g.quaternion)[i];
@@ -580,12 +616,15 @@ namespace gs {
 
 // The instantiations are exactly these: (L 0..3) x (depth row) x { the camera form | (abs row) x { kAdam 1, 2, 3 | the
 // anti-aliased form | the plain form } } -- the camera form stores no statistic and has no kAbsRow instantiation, the
-// anti-aliased form exists only for kAdam == 0 without the camera gradient (the kernel's static_asserts)
+// anti-aliased form exists only for kAdam == 0 without the camera gradient (the kernel's static_asserts); the plain form
+// and kAdam 1 also as kDirSums
 int launch_preprocess_bwd(const PreprocessBwdArgs &a, hipStream_t st) {
   GS_REQUIRE(a.span > 0, "nothing to launch");
   GS_REQUIRE(a.adam_mode >= 0 && a.adam_mode <= 3 && (a.adam_mode == 0 || a.adam != nullptr), "bad Adam form");
   GS_REQUIRE(!a.cam_rows || (a.adam_mode == 0 && !a.antialiased), "the camera gradient is a form of the plain backward");
   GS_REQUIRE(!a.antialiased || a.adam_mode == 0, "anti-aliased mode is a form of the plain backward");
+  GS_REQUIRE(!a.dir_sums || (a.adam_mode <= 1 && !a.cam_rows && !a.antialiased),
+             "the direction sums are read by the plain form and by adam_mode 1 only");
   const gsplat_gradients &g = a.out;
   const BwdOut o = {g.grad_xyz, g.grad_rgb, g.grad_sh, g.grad_opacity, g.grad_scale, g.grad_quaternion, g.grad_conic,
                     g.grad_uv, g.grad_J, g.grad_sigma, g.grad_xyz_c, g.grad_precompute_rgb, a.common, a.uv_norm};
@@ -601,7 +640,7 @@ int launch_preprocess_bwd(const PreprocessBwdArgs &a, hipStream_t st) {
   auto launch = [&](auto kernel) {
     kernel<<<grid, block, 0, st>>>(a.g, a.view, a.proj, a.M, a.c2g, a.xyz_c, a.rows, a.fx, a.fy, a.tan_fovx, a.tan_fovy,
                                    a.fwd_tan_fovx, a.fwd_tan_fovy, a.mh_dist, a.campos[0], a.campos[1], a.campos[2], a.width,
-                                   a.height, o, a.ranged, a.first, a.end, ad, a.cam_rows);
+                                   a.height, o, a.ranged, a.first, a.end, ad, a.cam_rows, a.dir_sums);
   };
   with_degree<0>(a.l_max, [&](auto L) {
     with_bool(a.rows_depth, [&](auto dr) {
@@ -610,10 +649,12 @@ int launch_preprocess_bwd(const PreprocessBwdArgs &a, hipStream_t st) {
       if (a.cam_rows) return launch(preprocess_bwd_kernel<kL, 0, kDR, true>);
       with_bool(a.rows_abs, [&](auto ab) {
         constexpr bool kAB = decltype(ab)::value;
-        if (a.adam_mode == 1) launch(preprocess_bwd_kernel<kL, 1, kDR, false, kAB>);
+        if (a.adam_mode == 1 && a.dir_sums) launch(preprocess_bwd_kernel<kL, 1, kDR, false, kAB, false, true>);
+        else if (a.adam_mode == 1) launch(preprocess_bwd_kernel<kL, 1, kDR, false, kAB>);
         else if (a.adam_mode == 3) launch(preprocess_bwd_kernel<kL, 3, kDR, false, kAB>);
         else if (a.adam_mode) launch(preprocess_bwd_kernel<kL, 2, kDR, false, kAB>);
         else if (a.antialiased) launch(preprocess_bwd_kernel<kL, 0, kDR, false, kAB, true>);
+        else if (a.dir_sums) launch(preprocess_bwd_kernel<kL, 0, kDR, false, kAB, false, true>);
         else launch(preprocess_bwd_kernel<kL, 0, kDR, false, kAB>);
       });
     });

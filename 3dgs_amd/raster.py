@@ -323,15 +323,23 @@ class RasterContext:
         are the same bits either way, gradients the same sums in another order."""
         check(self._lib.gsplat_context_set_compact_lists(self._h, int(bool(enabled))))
 
+    def set_dir_sums(self, enabled):
+        """The SH direction sums (gsplat_context_set_dir_sums; on by default): from the next forward on, the fused per-gaussian
+        forward leaves the nine sums over each SH row that the backward needs, and the plain per-gaussian backward and
+        backward_gaussians_adam with mode 1 read those instead of the rows (the other forms read the rows: a context that
+        only runs those should switch this off -- the sums cost the forward about 10 us per 1e6 gaussians).  Forward outputs and gradients are the same bits either way."""
+        check(self._lib.gsplat_context_set_dir_sums(self._h, int(bool(enabled))))
+
     def counters(self):
         """What the context's forwards did so far (gsplat_context_get_counters).  useful_entries is summed on the device's
         results when asked for: this call waits for the device."""
-        v = (ctypes.c_longlong * 12)()
-        self._lib.gsplat_context_get_counters(self._h, v, 12)
+        v = (ctypes.c_longlong * 14)()
+        self._lib.gsplat_context_get_counters(self._h, v, 14)
         return dict(forwards=int(v[0]), tail_redone=int(v[1]), compact_walks=int(v[2]), instance_growths=int(v[3]),
                     ordered_backwards=int(v[4]), segmented_backwards=int(v[5]), segmented_forwards=int(v[6]),
                     longest_chain=int(v[7]), chain_sum=int(v[8]), segment_fallbacks=int(v[9]),
-                    compact_list_backwards=int(v[10]), useful_entries=int(v[11]))
+                    compact_list_backwards=int(v[10]), useful_entries=int(v[11]),
+                    dir_sums_backwards=int(v[12]), dir_sums_fallbacks=int(v[13]))
 
     def set_timing(self, enabled, stages=None):
         """Per-stage HIP-event timing on / off; `stages`: names from STAGES to time only those (each timed stage costs

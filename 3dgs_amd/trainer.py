@@ -325,6 +325,9 @@ class Trainer:
         ctx.set_lean_forward(True)  # the loop only runs the fused backward, which recomputes Sigma / J / conic
         ctx.set_absgrad(bool(self.cfg["absgrad"]))
         ctx.set_antialiased(bool(self.cfg["antialiased"]))
+        # the forward leaves the SH direction sums only where the iteration's backward reads them: the plain backward and
+        # the one with the small groups' Adam inside; the other two forms read the rows, and the sums would be dead weight
+        ctx.set_dir_sums(self.fused_adam in (0, 1))
         if self._depth_keys():  # (all off: the context is never put in depth mode)
             ctx.set_depth(True, inverse=bool(self.cfg["distortion_inverse"]), moment=bool(self.cfg["distortion"]))
         return ctx

@@ -900,8 +900,10 @@ int gsplat_context_set_preprocess_split(gsplat_context *ctx, int mode);
  * in front ran out and which multiplied the transmittance product up themselves (results identical; every one of them
  * is work done twice).  out[10] compositing backwards that walked compact lists (gsplat_context_set_compact_lists), out[11]
  * the useful entries of the last forward's tile lists -- the sum over the tiles of what their workgroups ranked; 0 when
- * that forward wrote no compact lists; asked for (n > 11), it waits for the device and copies one int per tile.  Writes
- * min(n, 12) values and returns 12. */
+ * that forward wrote no compact lists; asked for (n > 11), it waits for the device and copies one int per tile.  out[12]
+ * per-gaussian backwards that read the forward's SH direction sums (gsplat_context_set_dir_sums), out[13] per-gaussian
+ * backwards that read the SH rows instead (every other form, and every backward whose forward left no sums it may use).
+ * Writes min(n, 14) values and returns 14. */
 int gsplat_context_get_counters(gsplat_context *ctx, long long *out, int n);
 /* Compact lists for the compositing backward (new entry point, no signature changed; default on).  A tile list holds
  * every gaussian whose mh_dist box touches the tile; about a quarter of the entries reach no 4x4 pixel block of the tile
@@ -915,6 +917,27 @@ int gsplat_context_get_counters(gsplat_context *ctx, long long *out, int n);
  * own longest list exceeds that hands over its full lists too).  GSPLAT_NO_COMPACT_LISTS=1 in the environment forces the
  * switch off. */
 int gsplat_context_set_compact_lists(gsplat_context *ctx, int enabled);
+/* The SH direction sums (new entry point, no signature changed; default on).  The per-gaussian backward needs the SH
+ * coefficient rows for one thing only: nine sums over the row, sum_k dY_k/d(axis) * coefficient[k][channel], from which the
+ * position gradient through the view direction is made (the coefficient gradients g_rgb[c] * Y_k need no coefficient).  With
+ * the switch on, the fused per-gaussian forward (SH degree 1 and up) of a context that is not render-only forms those sums while the row is in
+ * its registers for the colour and stores them (36 bytes per visible gaussian); gsplat_backward_gaussians / _range / _split
+ * and gsplat_backward_pass* in their plain form, and gsplat_backward_gaussians_adam with mode 1, then read the sums instead
+ * of the row, band 0 and the camera-space position (204 bytes).  The sums are the backward's own, formed by the same code in the same order on the same inputs: every output
+ * of the forward and every gradient is bit for bit what it is with the switch off.  A backward reads the sums only of the
+ * forward it differentiates, at that forward's degree, given the parameter arrays and camera centre that forward was given;
+ * forwards that do not write them (two-kernel forms, anti-aliased mode, render-only contexts) leave none, an Adam backward
+ * (which steps parameters in place) leaves them nobody's, and the Adam modes 0 and 2, the camera and the anti-aliased forms
+ * of the backward never read them: all of those read the rows, as before.  The sums cost the forward about 10 us per 1e6
+ * gaussians at degree 3: a context whose backwards are all of a form that does not read them should switch them off (the
+ * Trainer does, from its Adam mode).  "Given the arrays" is a comparison of POINTERS: a caller that rewrites xyz, rgb, sh or
+ * the view matrix in place between a forward and its backward gets the forward's sums and a camera-space position
+ * recomputed from the arrays as they then are, where the path that reads the rows takes the rows as they then are and the
+ * position the forward stored -- neither is the gradient of that forward; do not do that.  Read by the next
+ * gsplat_rasterize_image (whether it writes the sums) and by every per-gaussian backward (whether it may read them).
+ * GSPLAT_NO_DIR_SUMS=1 in the environment forces the switch off, whatever is set.  gsplat_context_get_counters out[12] /
+ * out[13] count the backwards of either kind. */
+int gsplat_context_set_dir_sums(gsplat_context *ctx, int enabled);
 int gsplat_context_set_timing(gsplat_context *ctx, int enabled);
 /* The same for a subset of the stages (bit k of stage_mask = stage k; 0 switches timing off).  Every timed stage
  * costs two event records per call, about 0.7 % of a 1 ms step each: bench.py times only stage 6 inside its timed
