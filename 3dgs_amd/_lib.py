@@ -242,6 +242,12 @@ SIGNATURES = {
     "gsplat_bilagrid_tv_loss": (_I, [_P, _I, _I, _I, _F, _I, _P, _P, _P]),
     "gsplat_vq_assign": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "gsplat_vq_update": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
+    "gsplat_tsdf_integrate": (_I, [_P, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F,
+                                   _P]),
+    "gsplat_tsdf_views_per_pass": (_I, []),
+    "gsplat_tsdf_mark": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "gsplat_tsdf_emit": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P,
+                              _P]),
     "gsplat_context_set_absgrad": (_I, [_P, _I]),
     "gsplat_context_set_compact_lists": (_I, [_P, _I]),
     "gsplat_context_set_dir_sums": (_I, [_P, _I]),

@@ -539,6 +539,114 @@ def vq_fit(x, K, iterations=10, seed=0):
     return codebook, index, objective
 
 
+TSDF_MAX_NODES = 2 ** 31 - 1  # GSPLAT_TSDF_MAX_NODES
+
+
+def tsdf_volume(origin, voxel, dims, color=True, device="cuda"):
+    """A zeroed TSDF volume: dict(tsdf [nz,ny,nx], weight [nz,ny,nx], color [nz,ny,nx,3] or None, origin, voxel, dims).
+    Node (i,j,k) sits at origin + voxel * (i,j,k); dims = (nx, ny, nz), x fastest in memory.  origin and voxel are kept as
+    the float32 values the kernels take (Python floats)."""
+    import numpy as np
+    nx, ny, nz = (int(d) for d in dims)
+    if min(nx, ny, nz) < 1 or nx * ny * nz > TSDF_MAX_NODES:
+        raise ValueError(f"dims must be positive and hold at most {TSDF_MAX_NODES} nodes")
+    origin = tuple(float(np.float32(v)) for v in origin)
+    voxel = float(np.float32(voxel))
+    if len(origin) != 3 or not all(np.isfinite(origin)) or not (np.isfinite(voxel) and voxel > 0.0):
+        raise ValueError("origin must be three finite numbers and voxel finite and positive")
+    z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)
+    return dict(tsdf=z(nz, ny, nx), weight=z(nz, ny, nx), color=z(nz, ny, nx, 3) if color else None, origin=origin,
+                voxel=voxel, dims=(nx, ny, nz))
+
+
+def _tsdf_grid(volume):
+    """The checked device arrays of a tsdf_volume -> (tsdf, weight, color or None, (nx, ny, nz), origin as float[3])."""
+    nx, ny, nz = (int(d) for d in volume["dims"])
+    tsdf, weight, color = volume["tsdf"], volume["weight"], volume.get("color")
+    for t, name, shape in ((tsdf, "tsdf", (nz, ny, nx)), (weight, "weight", (nz, ny, nx)), (color, "color", (nz, ny, nx, 3))):
+        if t is None and name == "color":
+            continue
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                or tuple(t.shape) != shape):
+            raise ValueError(f"volume['{name}'] must be a contiguous float32 device tensor of shape {shape}")
+    return tsdf, weight, color, (nx, ny, nz), (ctypes.c_float * 3)(*[float(v) for v in volume["origin"]])
+
+
+def _host_rows(t, name, rows, cols):
+    """[rows, cols] float32 on the host (from a tensor, device or not, or anything numpy takes), as a ctypes pointer."""
+    import numpy as np
+    a = np.ascontiguousarray((t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)), dtype=np.float32)
+    if a.shape != (rows, cols):
+        raise ValueError(f"{name} must be [{rows},{cols}]")
+    return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def tsdf_integrate(volume, depth, T, view, intrinsics, image=None, inverse=False, alpha_min=0.5, trunc=None, near=0.0,
+                   max_depth=0.0, max_weight=0.0):
+    """Fuse K views of one size into `volume` in place (gsplat_tsdf_integrate): depth, T [K,H,W] as a depth-mode forward
+    renders them (`inverse`: the forward composited 1/z), image [K,H,W,3] exactly when the volume has colour, view [K,12]
+    row-major [R|t] (the first twelve numbers of a camera dict's view), intrinsics [K,4] as pixel_intrinsics gives them.
+    Per node and view, in batch order: skip unless z > near, the nearest pixel lies in the image, is ok (1 - T >= alpha_min,
+    depth > 0) and its surface depth d = depth / (1 - T) is at most max_depth (<= 0: no limit) and d - z >= -trunc; then
+    tsdf = (w tsdf + min(1, (d - z) / trunc)) / (w + 1), colour likewise, w = min(w + 1, max_weight) (<= 0: no cap).
+    trunc: 4 voxels unless given.  The volume is read and written once per gsplat_tsdf_views_per_pass() views, and a batch
+    is bit for bit its views one call at a time.  Returns the volume."""
+    tsdf, weight, color, (nx, ny, nz), origin = _tsdf_grid(volume)
+    for t, name in ((depth, "depth"), (T, "T")):
+        if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
+                or t.dim() != 3 or t.shape != depth.shape):
+            raise ValueError(f"{name} must be a contiguous [K,H,W] float32 device tensor")
+    K, H, W = (int(s) for s in depth.shape)
+    if (image is None) != (color is None):
+        raise ValueError("image goes with a volume that has colour, and only with one")
+    if image is not None and (not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or not image.is_cuda
+                              or not image.is_contiguous() or tuple(image.shape) != (K, H, W, 3)):
+        raise ValueError("image must be a contiguous [K,H,W,3] float32 device tensor")
+    if K == 0:
+        return volume
+    view_a, view_p = _host_rows(view, "view", K, 12)
+    intr_a, intr_p = _host_rows(intrinsics, "intrinsics", K, 4)
+    trunc = 4.0 * volume["voxel"] if trunc is None else trunc
+    check(_lib.load().gsplat_tsdf_integrate(
+        _p(tsdf), _p(weight), _p(color), nx, ny, nz, origin, float(volume["voxel"]), _p(depth), _p(T), _p(image), view_p,
+        intr_p, K, H, W, int(bool(inverse)), float(alpha_min), float(trunc), float(near), float(max_depth),
+        float(max_weight), _stream()))
+    return volume
+
+
+def tsdf_extract(volume, min_weight=1.0):
+    """The zero level set of a TSDF volume as an indexed triangle mesh -> (vertices [Nv,3] float32, faces [Nf,3] int32,
+    colors [Nv,3] float32 or None), device tensors; marching tetrahedra on the Freudenthal split of every cell whose eight
+    nodes have weight >= min_weight (gsplat_tsdf_mark, a prefix sum, gsplat_tsdf_emit; include/gsplat_hip.h states the
+    vertex, face and winding order).  Watertight wherever the observed cells are; (v1 - v0) x (v2 - v0) points from inside
+    (tsdf < 0) to outside.  No atomics and no sort: two runs give the same bits.  One read-back (the two totals)."""
+    tsdf, weight, color, (nx, ny, nz), origin = _tsdf_grid(volume)
+    dev, n = tsdf.device, nx * ny * nz
+    lib = _lib.load()
+    cell_ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    edge_mask = torch.empty(n, dtype=torch.uint8, device=dev)
+    tri_count = torch.empty(n, dtype=torch.int32, device=dev)
+    vert_count = torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib.gsplat_tsdf_mark(_p(tsdf), _p(weight), nx, ny, nz, float(min_weight), _p(cell_ok), _p(tri_count),
+                               _p(edge_mask), _p(vert_count), _stream()))
+    vert_offset = torch.cumsum(vert_count, 0, dtype=torch.int64)
+    tri_offset = torch.cumsum(tri_count, 0, dtype=torch.int64)
+    num_vertices, num_faces = (int(v) for v in torch.stack((vert_offset[-1], tri_offset[-1])).tolist())  # the read-back
+    if num_vertices > 2 ** 31 - 1 or num_faces > 2 ** 31 - 1:
+        raise ValueError("the mesh has more than 2^31 - 1 vertices or faces: extract at a coarser resolution")
+    vert_offset -= vert_count  # inclusive -> exclusive
+    tri_offset -= tri_count
+    del vert_count, tri_count
+    vertices = torch.empty(num_vertices, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(num_faces, 3, dtype=torch.int32, device=dev)
+    colors = None if color is None else torch.empty(num_vertices, 3, dtype=torch.float32, device=dev)
+    if num_vertices or num_faces:
+        check(lib.gsplat_tsdf_emit(_p(tsdf), _p(color) if num_vertices else None, nx, ny, nz, origin,
+                                   float(volume["voxel"]), _p(cell_ok), _p(edge_mask), _p(vert_offset), _p(tri_offset),
+                                   num_vertices, num_faces, _p(vertices), _p(colors), _p(faces), _stream()))
+    return vertices, faces, colors
+
+
 def compute_psnr(predicted_data, gt_data, rows, cols):
     out = ctypes.c_float(0.0)
     check(_lib.load().gsplat_compute_psnr(_p(predicted_data), _p(gt_data), rows, cols, ctypes.byref(out), _stream()))

@@ -812,6 +812,72 @@ int gsplat_vq_assign(const float *x, const float *codebook, int N, int D, int K,
 int gsplat_vq_update(const float *x, const int *order, const int *start, int N, int D, int K, float *codebook,
                      void *stream);
 
+/* TSDF fusion of rendered depth maps and mesh extraction (no ABI bump: new entry points only; gs_tsdf.hip; the last step
+ * of 2DGS, RaDe-GS and GOF: "A Volumetric Method for Building Complex Models from Range Images", Curless & Levoy 1996).
+ * The volume is a dense grid of nodes p(i,j,k) = origin + voxel (i,j,k), 0 <= i < nx and likewise j, k, x fastest in
+ * memory, in caller-owned device arrays: tsdf [nz,ny,nx] (meaningful only where weight > 0), weight [nz,ny,nx] (a count
+ * of observations), color [nz,ny,nx,3] or NULL.  origin: three HOST floats.  A grid holds at most GSPLAT_TSDF_MAX_NODES
+ * nodes (indices of nodes, vertices and faces are 31-bit).  Everything is evaluated in double from the float inputs and
+ * rounded to float once; every kernel gathers (one thread per node, x on the lanes), nothing is added atomically, two
+ * runs give the same bits.
+ *   gsplat_tsdf_integrate  num_views views of one size: depth, T [num_views,rows,cols] and image [num_views,rows,cols,3]
+ *                     (NULL exactly when color is) on the device; view [num_views,12] (row-major [R|t]) and intrinsics
+ *                     [num_views,4] = (fx, fy, cx, cy), integer pixel coordinates being the sample points, on the HOST.
+ *                     For every node and the views in order: x_c = R p + t, z = x_c.z, skip unless z > near;
+ *                     u = fx x_c.x / z + cx, v = fy x_c.y / z + cy, the pixel (floor(u + 0.5), floor(v + 0.5)), skip when
+ *                     it is outside the image; skip unless the pixel is ok as gsplat_depth_to_normal defines it
+ *                     (A = 1 - T >= alpha_min, depth > 0, both finite); d = depth / A (inverse: A / depth), skip when
+ *                     max_depth > 0 and d > max_depth; s = d - z, skip when s < -trunc (hidden behind the surface);
+ *                     val = min(1, s / trunc) (free space in front of the surface is carved); with the node's weight w:
+ *                     tsdf = (w tsdf + val) / (w + 1), color likewise from the pixel's, w = w + 1, capped at max_weight
+ *                     when max_weight > 0.  The state is float and rounded once per view, and lives in registers over up
+ *                     to gsplat_tsdf_views_per_pass() views: the volume is read and written once per that many views, and
+ *                     a batch is bit for bit its views one call at a time.  num_views = 0: a successful no-op.
+ *                     Refused with GSPLAT_ERR_INVALID_ARG before anything is launched: a non-positive grid or image size,
+ *                     a negative num_views, more than GSPLAT_TSDF_MAX_NODES nodes, voxel or trunc not finite and
+ *                     positive, alpha_min outside (0, 1], image without color or the reverse, and (num_views > 0) a NULL
+ *                     tsdf, weight, origin, depth, T, view or intrinsics, intrinsics that are not finite, fx or fy 0.
+ *   gsplat_tsdf_mark  the counting step of marching tetrahedra on the Freudenthal split: with the corners of a cell
+ *                     numbered by bits (x = 1, y = 2, z = 4) its six tetrahedra are {0, a, a|b, 7} for the orderings
+ *                     (a, b, c) of the axes; they share the body diagonal and cut every face from its low to its high
+ *                     corner, so neighbouring cells agree on their shared face and the surface is closed by construction.
+ *                     A node is inside when tsdf < 0 (0 is outside).  A cell is meshed when all eight nodes have
+ *                     weight >= min_weight.  Per node n (arrays of the grid's size): cell_ok[n] = the cell whose low
+ *                     corner n is is meshed; tri_count[n] = that cell's triangles (0 .. 12); edge_mask[n] bit e = the
+ *                     edge of type e from n towards +x, +y, +z, +xy, +xz, +yz, +xyz (e = 0 .. 6) has one end inside and
+ *                     belongs to a meshed cell: it carries ONE vertex, shared by every triangle around it;
+ *                     vert_count[n] = the number of those bits.
+ *   gsplat_tsdf_emit  vert_offset / tri_offset [nodes]: the exclusive prefix sums of vert_count / tri_count, num_vertices
+ *                     and num_faces their totals (the caller scans and reads the two totals back).  Vertex order is
+ *                     (lower node's linear index, edge type); the vertex of the edge (a, b), a the lower node, is
+ *                     p_a + t (p_b - p_a), t = f_a / (f_a - f_b), its colour (vertex_colors, NULL exactly when color is)
+ *                     the same interpolation of the nodes' colours.  Face order is (cell's low corner's linear index,
+ *                     tetrahedron in the lexicographic order of (a, b, c): xyz, xzy, yxz, yzx, zxy, zyx, then the one or
+ *                     two triangles): with the tetrahedron's corners numbered 0..3 = (0, a, a|b, 7), one inside corner i
+ *                     and the others (o0, o1, o2) ascending, o1 and o2 swapped when (i, o0, o1, o2) is an odd
+ *                     permutation, give the triangle on the edges (i-o0, i-o1, i-o2); one outside corner: the same about
+ *                     it with the last two swapped; two inside corners i0 < i1 and the others o0 < o1, swapped when
+ *                     (i0, i1, o0, o1) is odd, give q = (i0-o0, i0-o1, i1-o1, i1-o0) as (q0, q1, q2) then (q0, q2, q3);
+ *                     for an odd ordering (a, b, c) every triangle's last two indices are swapped.  So
+ *                     (v1 - v0) x (v2 - v0) points from inside to outside, along +grad tsdf, towards the cameras.  A
+ *                     vertex on a node (t = 0) gives zero-area triangles, which are kept: the topology stays closed.
+ *                     Writes outside [0, num_vertices) / [0, num_faces) are dropped, not made.
+ * mark and emit are refused with GSPLAT_ERR_INVALID_ARG before anything is launched for a non-positive or too large grid,
+ * a NULL required pointer, a NaN min_weight, voxel not finite and positive, totals outside 0 .. 2^31 - 1. */
+#define GSPLAT_TSDF_MAX_NODES 2147483647LL
+int gsplat_tsdf_integrate(float *tsdf, float *weight, float *color /* or NULL */, int nx, int ny, int nz,
+                          const float *origin, float voxel, const float *depth, const float *T,
+                          const float *image /* or NULL */, const float *view, const float *intrinsics, int num_views,
+                          int rows, int cols, int inverse, float alpha_min, float trunc, float near, float max_depth,
+                          float max_weight, void *stream);
+int gsplat_tsdf_views_per_pass(void);
+int gsplat_tsdf_mark(const float *tsdf, const float *weight, int nx, int ny, int nz, float min_weight,
+                     unsigned char *cell_ok, int *tri_count, unsigned char *edge_mask, int *vert_count, void *stream);
+int gsplat_tsdf_emit(const float *tsdf, const float *color /* or NULL */, int nx, int ny, int nz, const float *origin,
+                     float voxel, const unsigned char *cell_ok, const unsigned char *edge_mask,
+                     const long long *vert_offset, const long long *tri_offset, long long num_vertices,
+                     long long num_faces, float *vertices, float *vertex_colors /* or NULL */, int *faces, void *stream);
+
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
  * tiles, stable radix sorts on (depth bits, tile).  1 / 2 force one route.  Both produce identical lists. */
