@@ -71,6 +71,17 @@ int reserve_instances(gsplat_context *c, size_t S, int num_tiles, hipStream_t st
   return GSPLAT_OK;
 }
 
+// the forward this context recorded (lists_ready), for the kernels that walk it again
+static ReplayArgs recorded_forward(gsplat_context *c) {
+  ReplayArgs a = {};
+  a.recs = c->recs.as<float4>();
+  a.sorted = c->sorted.as<int>(); a.ranges = c->ranges.as<int>();
+  a.n_px = c->n_px.as<int>(); a.T_px = c->T_px.as<float>();
+  a.c2g = c->c2g.as<int>();
+  a.width = c->width; a.height = c->height;
+  return a;
+}
+
 }  // namespace gs
 
 extern "C" {
@@ -224,9 +235,7 @@ int gsplat_context_accumulate_contributions(gsplat_context *c, int num_gaussians
   if (weight_sum) GS_REQUIRE_DEV(weight_sum);
   if (weight_max) GS_REQUIRE_DEV(weight_max);
   if (pixels) GS_REQUIRE_DEV(pixels);
-  return gs::launch_contributions(c->recs.as<float4>(), c->sorted.as<int>(), c->ranges.as<int>(), c->n_px.as<int>(),
-                                  c->c2g.as<int>(), c->width, c->height, weight_sum, weight_max, pixels,
-                                  (hipStream_t)stream);
+  return gs::launch_contributions(gs::recorded_forward(c), weight_sum, weight_max, pixels, (hipStream_t)stream);
 }
 
 int gsplat_context_render_features(gsplat_context *c, int num_gaussians, int channels, const float *features, float *out,
@@ -238,8 +247,7 @@ int gsplat_context_render_features(gsplat_context *c, int num_gaussians, int cha
   GS_REQUIRE(channels >= 1 && channels <= 512, "channels must be 1 .. 512");
   GS_REQUIRE_DEV(features);
   GS_REQUIRE_DEV(out);
-  return gs::launch_features_fwd(c->recs.as<float4>(), c->sorted.as<int>(), c->ranges.as<int>(), c->n_px.as<int>(),
-                                 c->c2g.as<int>(), c->width, c->height, channels, features, out, (hipStream_t)stream);
+  return gs::launch_features_fwd(gs::recorded_forward(c), channels, features, out, (hipStream_t)stream);
 }
 
 int gsplat_context_lift_features(gsplat_context *c, int num_gaussians, int channels, const float *map, float *lifted,
@@ -250,8 +258,7 @@ int gsplat_context_lift_features(gsplat_context *c, int num_gaussians, int chann
   GS_REQUIRE(channels >= 1 && channels <= 512, "channels must be 1 .. 512");
   GS_REQUIRE_DEV(map);
   GS_REQUIRE_DEV(lifted);
-  return gs::launch_features_lift(c->recs.as<float4>(), c->sorted.as<int>(), c->ranges.as<int>(), c->n_px.as<int>(),
-                                  c->c2g.as<int>(), c->width, c->height, channels, map, lifted, (hipStream_t)stream);
+  return gs::launch_features_lift(gs::recorded_forward(c), channels, map, lifted, (hipStream_t)stream);
 }
 
 int gsplat_context_features_backward(gsplat_context *c, int num_gaussians, int channels, const float *features,
@@ -268,9 +275,8 @@ int gsplat_context_features_backward(gsplat_context *c, int num_gaussians, int c
              "features must be a device pointer");
   GS_REQUIRE(grad_map != nullptr && gs::check_device_ptr(grad_map, "grad_map", __func__) == GSPLAT_OK,
              "grad_map must be a device pointer");
-  return gs::launch_features_bwd(c->recs.as<float4>(), c->sorted.as<int>(), c->ranges.as<int>(), c->n_px.as<int>(),
-                                 c->T_px.as<float>(), c->c2g.as<int>(), c->width, c->height, channels, features, grad_map,
-                                 c->grad_rows.as<float>(), (hipStream_t)stream);
+  return gs::launch_features_bwd(gs::recorded_forward(c), channels, features, grad_map, c->grad_rows.as<float>(),
+                                 (hipStream_t)stream);
 }
 
 int gsplat_context_depth_map(gsplat_context *c, const float **depth) {

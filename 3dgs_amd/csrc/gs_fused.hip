@@ -3,11 +3,11 @@
 // of TrainerImpl::backward_pass, cuda/trainer.cu:941-1012).  No kernel lives here: every launch is a launcher of gs_launch.h.
 //
 // Forward:   project_cull -> preprocess<L> (gs_preprocess.hip) -> bin_offsets -> bin_scatter -> tile_depth_sort_*
-//            (gs_binning.hip) -> render_fwd (gs_render.hip): the sparse route; dense scenes and very large tile grids take
+//            (gs_binning.hip) -> render_fwd (gs_render_fwd.hip): the sparse route; dense scenes and very large tile grids take
 //            radix sorts.  ONE host read-back, the record bin_scatter publishes: everything behind the counts is queued
 //            BEFORE the host waits for it, bounded by gs::instance_room(), and queued again if the record shows that it did
 //            not fit (decisions: gs_forward_plan.h).
-// Backward:  zero gradient rows -> compositing backward (64-byte row atomics, gs_render.hip) -> one fused per-gaussian
+// Backward:  zero gradient rows -> compositing backward (64-byte row atomics, gs_render_bwd.hip) -> one fused per-gaussian
 //            kernel for the whole SH / conic / Jacobian / Sigma / projection chain (gs_preprocess_bwd.hip).
 // The reference runs ~20 thrust compactions, ~15 kernels and 5 blocking read-backs for the
 // same work; results are laid out exactly like its ForwardPassData / GaussianGradients.

@@ -13,6 +13,7 @@ struct TileSegments;  // gs_render.h
 struct FwdSegments;
 struct RenderFwdArgs;
 struct RenderBwdArgs;
+struct ReplayArgs;
 struct CullArgs;  // gs_pergaussian_args.h
 struct PreprocessArgs;
 struct ShColourArgs;
@@ -44,28 +45,27 @@ int launch_tile_emit(const float *uv, const float *xyz_c, const float *radius, i
                      const unsigned long long *hitmask, long long capacity, unsigned int *tkeys,
                      unsigned long long *payload, hipStream_t st);
 
-// ---- gs_render.hip.  The two compositing launchers take their arguments by name (gs_render.h: RenderFwdArgs,
-// RenderBwdArgs).  launch_render_bwd stamps ev_start / ev_stop from the dispatch itself when both are given, whichever
-// kernel it selects (until the argument structs only the packed-records-and-rows forms did; no caller times another).
+// ---- gs_render_fwd.hip, gs_render_bwd.hip.  The two compositing launchers take their arguments by name (gs_render.h:
+// RenderFwdArgs, RenderBwdArgs).  launch_render_bwd stamps ev_start / ev_stop from the dispatch itself when both are
+// given, whichever kernel it selects (until the argument structs only the packed-records-and-rows forms did; no caller
+// times another).
 int launch_render_fwd(const RenderFwdArgs &a, hipStream_t st);
-int launch_render_bwd(const RenderBwdArgs &a, hipStream_t st);
 int launch_fwd_segments_table(const int *ranges, int num_tiles, const FwdSegments &fs, hipStream_t st);
+int launch_render_bwd(const RenderBwdArgs &a, hipStream_t st);
 int launch_tile_segments(const int *ranges, const int *tops, int num_tiles, const TileSegments &seg, hipStream_t st);
-int launch_contributions(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
-                         int width, int height, float *weight_sum, float *weight_max, int *pixels, hipStream_t st);
-// the caller's channels through the recorded forward's weights and back (features_fwd_kernel, features_lift_kernel):
-// features [N,C] in global order -> out [H,W,C]; map [H,W,C] -> lifted [N,C] in global order, accumulated into
-int launch_features_fwd(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
-                        int width, int height, int channels, const float *features, float *out, hipStream_t st);
-int launch_features_lift(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const int *c2g,
-                         int width, int height, int channels, const float *map, float *lifted, hipStream_t st);
-// the feature map's gradient with respect to the geometry (features_bwd_kernel): features [N,C] in global order and
-// grad_map [H,W,C] -> columns 3..8 (opacity logit, conic, uv) of the gradient rows [M,16], added to what they hold
-int launch_features_bwd(const float4 *recs, const int *sorted, const int *ranges, const int *n_px, const float *T_px,
-                        const int *c2g, int width, int height, int channels, const float *features, const float *grad_map,
-                        float *rows, hipStream_t st);
 int launch_tile_order(const int *work, const int *ranges, int num_tiles, int *order, hipStream_t st);
 bool tile_order_supported(int num_tiles);
+
+// ---- gs_replay.hip: the kernels that walk a recorded forward again (gs_render.h: ReplayArgs)
+int launch_contributions(const ReplayArgs &a, float *weight_sum, float *weight_max, int *pixels, hipStream_t st);
+// the caller's channels through the recorded forward's weights and back (features_fwd_kernel, features_lift_kernel):
+// features [N,C] in global order -> out [H,W,C]; map [H,W,C] -> lifted [N,C] in global order, accumulated into
+int launch_features_fwd(const ReplayArgs &a, int channels, const float *features, float *out, hipStream_t st);
+int launch_features_lift(const ReplayArgs &a, int channels, const float *map, float *lifted, hipStream_t st);
+// the feature map's gradient with respect to the geometry (features_bwd_kernel): features [N,C] in global order and
+// grad_map [H,W,C] -> columns 3..8 (opacity logit, conic, uv) of the gradient rows [M,16], added to what they hold
+int launch_features_bwd(const ReplayArgs &a, int channels, const float *features, const float *grad_map, float *rows,
+                        hipStream_t st);
 
 // ---- gs_filter3d.hip: the 3D smoothing filter's parameter transform and its chain rule (gsplat_context_set_filter3d)
 int launch_filter3d_apply(const float *scale, const float *opacity, const float *filter3d, int N, float *scale_eff,

@@ -1,7 +1,9 @@
-// gs_render.h -- device helpers shared by the compositing kernels (gs_render.hip) and the
-// fused preprocess kernel (gs_preprocess.hip): the 48-byte "splat record" a tile stages in LDS,
-// wave64 cross-lane reductions on DPP, and the XCD-aware block -> tile map.
+// gs_render.h -- device helpers shared by the compositing kernels (gs_render_fwd.hip, gs_render_bwd.hip), the kernels
+// that replay a recorded forward (gs_replay.hip) and the fused preprocess kernel (gs_preprocess.hip): the 48-byte
+// "splat record" a tile stages in LDS, wave64 cross-lane reductions on DPP, the XCD-aware block -> tile map, the
+// launchers' argument structs, and the batch staging and row lists of the tile walk.
 #pragma once
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -156,6 +158,10 @@ template <int kCtrl>
 __device__ __forceinline__ float dpp_add(float v) {
   const int moved = __builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, 0xF, 0xF, false);
   return v + __int_as_float(moved);
+}
+template <int kCtrl>
+__device__ __forceinline__ float dpp_take(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), kCtrl, 0xF, 0xF, false));
 }
 __device__ __forceinline__ float row_sum(float v) {  // every lane of a 16-lane row ends with the row total
   v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
@@ -536,7 +542,7 @@ __device__ __forceinline__ int block_to_tile(int block, int num_tiles) {
   return (block & 7) * per_xcd + (block >> 3);
 }
 static inline int tile_grid(int num_tiles) { return ((num_tiles + 7) >> 3) * 8; }
-// r04: the same map through an optional order table (tile_order_kernel, gs_render.hip): slot s of the table holds the tile
+// r04: the same map through an optional order table (tile_order_kernel, gs_render_bwd.hip): slot s of the table holds the tile
 // that the block mapped to slot s should take -- every XCD's run of tiles re-ordered heaviest first, so that the
 // launch's last round is made of its lightest tiles (entries >= num_tiles: padding)
 __device__ __forceinline__ int ordered_tile(const int *__restrict__ order, int block, int num_tiles) {
@@ -544,6 +550,7 @@ __device__ __forceinline__ int ordered_tile(const int *__restrict__ order, int b
   return order ? order[slot] : slot;
 }
 constexpr int kOrderMaxRun = 2048;  // tiles per XCD run the order kernel handles (16384 tiles: the counting-sort limit)
+constexpr int kTableChunks = 16;    // tiles per thread of the one-workgroup segment tables (tile_segments_kernel, fwd_segments_table_kernel)
 
 // r05 -- long tile lists, split for the BACKWARD.  One workgroup walks one tile's list batch after batch: a list of ten
 // thousand entries is eighty batches in a row, and on a trained capture (lists of 1100 entries on average, 9800 at most)
@@ -745,5 +752,124 @@ struct RenderBwdArgs {
   DepthMaps depth;  // depth mode: needs recs and out.rows
   bool absgrad;     // likewise
 };
+// A recorded forward, as the kernels that walk it again take it (gs_replay.hip): the context's packed records, the full
+// tile lists and the forward's per-pixel outputs.
+struct ReplayArgs {
+  const float4 *recs;
+  const int *sorted, *ranges;  // the tile lists
+  const int *n_px;             // [H,W] the forward's stop indices ...
+  const float *T_px;           // ... and final transmittances (read by features_bwd_kernel only)
+  const int *c2g;              // compact_to_global
+  int width, height;
+};
+
+// ---- what the compositing and the replay kernels share of the tile walk -----------------------------------------------
+// Diagnostic build (-DGS_STAMP=1, tools/bwd_timeline.py): every wave of render_fwd / render_bwd records where its cycles
+// went (s_memtime around the barriers, staging, list building, the trip loop and the flush) into a device array of its
+// file that gsplat_debug_read_stamps[_fwd] copies out.  No stamp code exists in the normal build.
+#ifndef GS_STAMP
+#define GS_STAMP 0
+#endif
+#if GS_STAMP
+#define GS_STAMP_WORDS 16
+#define GS_NOW() ((unsigned long long)__builtin_readcyclecounter())
+#define GS_LAP(acc) do { const unsigned long long _n = GS_NOW(); (acc) += _n - st_last; st_last = _n; } while (0)
+#else
+#define GS_LAP(acc) do { } while (0)
+#endif
+// Backward batch size: 124 slots keep the block at 20 392 B of LDS (records 4 KB, f64 accumulators 9.7 KB, lists + third
+// record array 5.8 KB), i.e. EIGHT workgroups per CU (160 KB / 8 = 20 480 B), matching the 64 VGPRs render_bwd_kernel is
+// held to: 8 waves per SIMD and 2048 resident workgroups, which 1080p's 8160 tiles fill in 3.98 rounds (r02: 0.350 ->
+// 0.342 ms against 128 slots / 72 VGPRs / 7 workgroups per CU).  256 slots (41 KB, 3 blocks/CU) measured 0.76 ms vs
+// 0.57 ms when tried in r01, 64 slots 0.63 ms (twice the barriers and per-batch work).
+#ifndef GS_BWD_BATCH
+#define GS_BWD_BATCH 124
+#endif
+
+// Forward batch size: 248 slots keep the block at 20 KB of LDS = EIGHT workgroups per CU at the kernel's 62 VGPRs (256
+// slots: 20 800 B, seven).  r02 measured +-0 for this; with r04's shorter loop it is -6 us (profiles/r04_ab_priority...).
+#ifndef GS_FWD_BATCH
+#define GS_FWD_BATCH 248
+#endif
+constexpr int kBatch = GS_FWD_BATCH;
+
+template <bool kPacked>
+__device__ __forceinline__ SplatRec load_record(int g, const float4 *__restrict__ recs, const RawSplats &raw) {
+  if constexpr (kPacked) {
+    SplatRec s;
+    s.r0 = recs[3 * g]; s.r1 = recs[3 * g + 1]; s.r2 = recs[3 * g + 2];
+    return s;
+  } else {
+    return make_record(raw.uv[2 * g], raw.uv[2 * g + 1], raw.conic[3 * g], raw.conic[3 * g + 1], raw.conic[3 * g + 2],
+                       raw.opacity[g], raw.rgb[3 * g], raw.rgb[3 * g + 1], raw.rgb[3 * g + 2]);
+  }
+}
+
+constexpr int kListStride = kBatch;  // entries per row list (a batch can put all of its 256 slots on one list)
+
+// bit of (wave, row) in the 16-bit block mask: block (bx, by) = ((wave & 1) * 2 + (row & 1), (wave >> 1) * 2 + (row >> 1))
+__device__ __forceinline__ int wave_first_bit(int wave) { return (wave >> 1) * 8 + (wave & 1) * 2; }
+
+struct RowCounts { int c0, c1, c2, c3; };
+
+// Compacts, for each of the wave's four rows, the slots of the staged batch that hit the row's block
+// (and lie below the row's stop index `lim*` in the backward).  `s_r2`: the record array whose .w holds the 16 block bits
+// (the backward's third array, the forward's second).  A list entry is the slot's byte offset into the
+// record arrays (slot * 16), so the loop needs no shift; counts are wave-uniform.
+template <int kStride>
+__device__ __forceinline__ RowCounts build_row_lists(const float4 *s_r2, unsigned short *lists, int count, int wave,
+                                                     int lane, int lim0, int lim1, int lim2, int lim3, int round,
+                                                     int slot0 = 0) {  // slot0: the record arrays' slot of `s_r2[0]` (r06: two sets)
+  RowCounts rc = {0, 0, 0, 0};
+  const int b0 = wave_first_bit(wave);
+  for (int sb = 0; sb < count; sb += 64) {
+    const int slot = sb + lane;
+    const unsigned int nib = slot < count ? (__float_as_uint(s_r2[slot].w) >> b0) : 0u;
+    const bool h0 = (nib & 1u) && slot < lim0, h1 = (nib & 2u) && slot < lim1;
+    const bool h2 = (nib & 16u) && slot < lim2, h3 = (nib & 32u) && slot < lim3;
+    const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
+    if ((m0 | m1 | m2 | m3) == 0ull) continue;
+#define GS_MBCNT(m) __builtin_amdgcn_mbcnt_hi((unsigned int)((m) >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)(m), 0u))
+    if (h0) lists[0 * kStride + rc.c0 + GS_MBCNT(m0)] = (unsigned short)((slot0 + slot) << 4);
+    if (h1) lists[1 * kStride + rc.c1 + GS_MBCNT(m1)] = (unsigned short)((slot0 + slot) << 4);
+    if (h2) lists[2 * kStride + rc.c2 + GS_MBCNT(m2)] = (unsigned short)((slot0 + slot) << 4);
+    if (h3) lists[3 * kStride + rc.c3 + GS_MBCNT(m3)] = (unsigned short)((slot0 + slot) << 4);
+#undef GS_MBCNT
+    rc.c0 += __popcll(m0); rc.c1 += __popcll(m1); rc.c2 += __popcll(m2); rc.c3 += __popcll(m3);
+  }
+  // Pad the shorter lists up to the wave's trip count (rounded up to `round`) with the sentinel slot kStride, whose
+  // record is all zeros (opacity 0 -> alpha 0): a row past the end of its list then needs no "am I active" test.
+  const int longest = max(max(rc.c0, rc.c1), max(rc.c2, rc.c3));
+  const int padded = (longest + round - 1) / round * round;
+  const unsigned short sentinel = (unsigned short)((slot0 + kStride) << 4);
+  for (int k = lane; k < padded; k += 64) {
+    if (k >= rc.c0) lists[0 * kStride + k] = sentinel;
+    if (k >= rc.c1) lists[1 * kStride + k] = sentinel;
+    if (k >= rc.c2) lists[2 * kStride + k] = sentinel;
+    if (k >= rc.c3) lists[3 * kStride + k] = sentinel;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  return rc;
+}
+
+__device__ __forceinline__ int row_max_int(int v) {  // max over the 16 lanes of a row, in every lane of the row
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));
+  v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));
+  return v;
+}
+
+// One launch of `kernel`, its arguments converted to its parameter types.  With both events it is a timed launch (the
+// context's per-stage timing): the events take the begin and end timestamps of THIS dispatch from its completion signal.
+// Two hipEventRecord calls around the launch are barrier packets of their own and kept the GPU idle for ~11 us before and
+// ~6 us after the kernel in every step they were on.
+template <typename... P>
+static void launch_tiles(void (*kernel)(P...), dim3 grid, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop,
+                         std::common_type_t<P>... args) {
+  if (ev_start && ev_stop) hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ev_start, ev_stop, 0, args...);
+  else kernel<<<grid, dim3(256), 0, st>>>(args...);
+}
 
 }  // namespace gs

@@ -17,7 +17,7 @@ float32).  feature_sums returns, per visible gaussian and for these six columns 
                 own terms are sum_c (|f_c| + |behind_c|) |G_c| T -- a sum over C channels of random sign, which is also
                 what the channel chunks of the kernel cancel among themselves.
 
-The walk is the kernel's (gs_render.hip: features_bwd_kernel), not compositing_sums': channels in chunks of CHUNK = 16,
+The walk is the kernel's (gs_replay.hip: features_bwd_kernel), not compositing_sums': channels in chunks of CHUNK = 16,
 every chunk with its own scalar s (t = d_i - s, s <- s + alpha t) and its own sums, the chunks' sums added at the end.
 In float64 that is the same number as compositing_sums' vector form to 1e-16 (tests/test_features_bwd_cpu.py holds it to
 the sum over channel triplets of compositing_sums itself).  dtype=np.float32 models the kernel's summation: d_i chained

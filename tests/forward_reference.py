@@ -56,7 +56,7 @@ compositing_sums walks backwards.  Per composited entry i of a pixel:
   a channel: sum_i |c_i| w_i (1 + rc + ra_i + rT_i) + |acc_i| (the running sum's own rounding) and at the end
       |bg| T_final (1 + rT_final) + |value|; rc is the colour's own error (0 for a stored colour, LIB for 1/z, 2 LIB + 1 for its
       square).  A pixel that composites nothing is bg exactly: unit 0.  alpha = 1 - T adds 1 + T.
-  the segmented forward (gs_render.hip: fwd_segments_combine_kernel, gs_render.h: TileSegments): a list longer than
+  the segmented forward (gs_render_fwd.hip: fwd_segments_combine_kernel, gs_render.h: TileSegments): a list longer than
       SEG_SPLIT_MIN is walked in segments of SEG_ENTRIES; a segment's partial colour is formed from the published prefix
       transmittance and added to the sum of the segments in front.  Per boundary a pixel passes: one more rounding of T
       (rT + 1) and of the sum (|acc| at the boundary), and once the segments' own products (sum |c| w).

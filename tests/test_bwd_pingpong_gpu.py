@@ -1,4 +1,4 @@
-"""r06 experiment: the backward with two half-batches in flight (gs_render.hip: render_bwd_pp_kernel, switched on by
+"""r06 experiment: the backward with two half-batches in flight (gs_render_bwd.hip: render_bwd_pp_kernel, switched on by
 GSPLAT_BWD_PINGPONG=1 per launch).  The same parity rows as the default kernel's: every test below is the test of
 tests/test_fused_gpu.py of the same name, run with the switch set -- small scenes against the oracle (all twelve gradient
 arrays), odd sizes, the cuda/render_backward.cu:170 gate, lists of 1 025 .. 10 000 entries, the segmented backward, large

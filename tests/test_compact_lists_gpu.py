@@ -10,7 +10,7 @@ from test_fused_gpu import _check_backward, _check_forward, _np
 
 pytestmark = pytest.mark.gpu
 
-FWD_BATCH, SEG_SPLIT_MIN = 248, 1488  # gs_render.hip: GS_FWD_BATCH; gs_render.h: kSegSplitMin
+FWD_BATCH, SEG_SPLIT_MIN = 248, 1488  # gs_render.h: GS_FWD_BATCH, kSegSplitMin
 LEAVES = ("xyz", "rgb", "sh", "opacity", "scale", "quaternion")
 INTERMEDIATES = ("conic", "uv", "J", "sigma", "xyz_c", "precompute_rgb")
 

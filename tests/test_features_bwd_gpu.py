@@ -126,6 +126,25 @@ def test_feature_loss_alone(gpu, name):
             _run(torch, ctx, case, dp, dc, C, f"{name}, forward {it}", K_OBS_FEATURES[name])
 
 
+@pytest.mark.parametrize("C", [4, 16])
+def test_an_unaligned_gradient_map_takes_the_scalar_path(gpu, C):
+    """C a multiple of 4, but grad_map starts one float past a 16-byte boundary: the kernel reads it float by float.  The
+    gradients agree with the aligned call's under the bar that call meets against the reference (float atomics)."""
+    torch, case = gpu, fc.make("partial")
+    raster, dp, dc = _on_device(case)
+    ctx = raster.RasterContext(case["N"], case["W"], case["H"])
+    t, aligned = _run(torch, ctx, case, dp, dc, C, "partial, aligned map", K_OBS_FEATURES["partial"])
+    fwd = ctx.rasterize_image(dp, dc, case["cfg"], 0.0, case["L"])
+    gmap = _cols(torch, case["gmap"], C)
+    offset = torch.empty(gmap.numel() + 1, device="cuda")[1:].view(gmap.shape).copy_(gmap)
+    assert offset.data_ptr() % 16 == 4 and offset.is_contiguous()
+    got = _feature_backward(torch, ctx, case, dp, dc, fwd, _cols(torch, case["feats"], C), offset)
+    against = dict(t, **{k: (aligned[k].astype(np.float64).reshape(np.shape(t[k][0])),) + tuple(t[k][1:]) for k in GROUPS})
+    _hold(against, got, K_OBS_FEATURES["partial"], f"partial, C = {C}: offset map against the aligned call")
+    for k in LEAVES:
+        assert_grad_close(got[k], aligned[k], f"partial, C = {C}: offset map against the aligned call, leaf {k}")
+
+
 def test_feature_loss_alone_on_small(gpu):
     """5000 gaussians at 256 x 144, lists of up to 150 entries, more than one round of workgroups per chunk: C = 16."""
     torch, case = gpu, fc.make("small")

@@ -117,6 +117,32 @@ def test_both_sides_match_the_reference(gpu, scene, orc, name):
         assert int(np.diff(case["ref"]["ranges"]).max()) == 150
 
 
+@pytest.mark.parametrize("C", [4, 16])
+def test_unaligned_maps_take_the_scalar_path(gpu, scene, orc, C):
+    """C a multiple of 4, but the [H,W,C] array starts one float past a 16-byte boundary: float-by-float accesses.  The
+    rendered map is order-fixed, so it equals the aligned call bit for bit; the lifted sums (float atomics) agree with
+    the aligned call's under the bar those meet against the reference."""
+    torch, case = gpu, _shared(scene, orc, "partial")
+    raster, dp, dc = _on_device(case)
+    N, W, H, L = case["N"], case["W"], case["H"], case["L"]
+    ctx = raster.RasterContext(N, W, H)
+    ctx.rasterize_image(dp, dc, scene.CONFIG, 0.0, L)
+    aligned = _both_sides(torch, ctx, case, C, "partial, aligned")
+
+    def offset_like(t):
+        v = torch.full((t.numel() + 1,), 7.0, device="cuda")[1:].view(t.shape)
+        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+        return v
+
+    into = offset_like(aligned)
+    assert ctx.render_features(_cols(torch, case["feats"], C), out=into) is into and torch.equal(into, aligned)
+    fmap = _cols(torch, case["fmap"], C)
+    want = ctx.lift_features(fmap, torch.zeros(N, C, device="cuda"))
+    got = ctx.lift_features(offset_like(fmap).copy_(fmap), torch.zeros(N, C, device="cuda"))
+    torch.cuda.synchronize()
+    _check_lifted(_np(got), _np(want).astype(np.float64), case["culled"], f"partial, C = {C}: offset map against the aligned call", fill=0.0)
+
+
 def test_long_lists_are_walked_whole(gpu, scene, orc):
     torch, raster = gpu, pkg("raster")
     N, W, H, L, params, cam = _long_list_scene(scene)

@@ -973,7 +973,7 @@ def test_forward_stops_where_the_pixels_saturate(gpu, scene):
 @pytest.mark.parametrize("form", ["plain", "full_lists", "depth", "absgrad", "pingpong"])
 def test_timed_backward_is_the_same_backward(gpu, scene, monkeypatch, form):
     """Timing stage 6 (render_backward) changes HOW the compositing backward is launched: the launch stamps the two events
-    itself instead of going out as a plain launch (gs_render.hip: launch_tiles).  Only the benchmark took that path.  Every
+    itself instead of going out as a plain launch (gs_render.h: launch_tiles).  Only the benchmark took that path.  Every
     backward form the launcher can select -- plain on the compact lists, plain on the full lists, depth, absgrad, ping-pong
     -- must give, timed, the gradients it gives untimed (rel 1e-4: the sums are atomic, as in
     test_tile_order_changes_nothing), leave the forward's outputs the same bits, and report one launch with a time.

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/ab/build_variant.sh <tag> <source.hip> [extra flags]: links tools/ab/lib<tag>.so from the current objects with
-# the object of the given source (its basename decides which: gs_render.hip, gs_binning.hip, ...) rebuilt from that file
+# the object of the given source (its basename decides which: gs_render_bwd.hip, gs_binning.hip, ...) rebuilt from that file
 # with the Makefile's flags plus the extra ones.  The library's objects are the Makefile's SRCS (make print-srcs).
 tag=$1; src=$(readlink -f "$2"); shift 2
 name=$(basename "$src" .hip)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/kernel_resources.sh <file.hip> [name filter] [extra flags]: VGPRs / SGPRs / LDS / scratch of every kernel
 # of one source file, compiled device-only with the Makefile's flags
-src=${1:-3dgs_amd/csrc/gs_render.hip}; pat=${2:-.}; shift 2
+src=${1:-3dgs_amd/csrc/gs_render_bwd.hip}; pat=${2:-.}; shift 2
 tmp=$(mktemp -d)
 hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -munsafe-fp-atomics -mllvm -amdgpu-atomic-optimizer-strategy=None \
   -I$(dirname $src) "$@" --cuda-device-only -c -o $tmp/dev.co $src 2>/dev/null || { echo "compile failed"; exit 1; }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VALU issue cost of render_bwd's trip loop, instruction by instruction: compiles gs_render.hip device-only, takes the
+"""VALU issue cost of render_bwd's trip loop, instruction by instruction: compiles gs_render_bwd.hip device-only, takes the
 innermost loop of render_bwd_kernel<true,true,*> and weighs every VALU instruction with the per-SIMD issue cost measured
 on MI355X (profiles/microbench/r01_valu_rate*.txt, cycles per wave64 instruction at 8 waves per SIMD, 2.4 GHz nominal).
 Prints cycles per trip and, with the trip count of the benchmark scene, the share of the kernel's SIMD cycles.
@@ -27,7 +27,7 @@ def main():
         out = os.path.join(tmp, "r.s")
         subprocess.check_call(["hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-munsafe-fp-atomics",
                                "-mllvm", "-amdgpu-atomic-optimizer-strategy=None", "--cuda-device-only", "-S", "-o", out,
-                               os.path.join(ROOT, "3dgs_amd", "csrc", "gs_render.hip")], stderr=subprocess.DEVNULL)
+                               os.path.join(ROOT, "3dgs_amd", "csrc", "gs_render_bwd.hip")], stderr=subprocess.DEVNULL)
         text = open(out).read().split("\n")
     start = next(i for i, l in enumerate(text) if l.startswith("_ZN2gs17render_bwd_kernelILb1ELb1"))
     body = []
