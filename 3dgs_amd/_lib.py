@@ -244,6 +244,11 @@ SIGNATURES = {
     "gsplat_vq_update": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
     "gsplat_tsdf_integrate": (_I, [_P, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F,
                                    _P]),
+    "gsplat_tsdf_integrate_surface": (_I, [_P, _P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F,
+                                           _P]),
+    "gsplat_context_median_depth": (_I, [_P, _I, _F, _P, _P, _P]),
+    "gsplat_mesh_components": (_I, [_P, _I, _I, _P, _P, _P, _P]),
+    "gsplat_mesh_compact": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "gsplat_tsdf_views_per_pass": (_I, []),
     "gsplat_tsdf_mark": (_I, [_P, _P, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "gsplat_tsdf_emit": (_I, [_P, _P, _I, _I, _I, _P, _F, _P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P,

@@ -238,6 +238,21 @@ int gsplat_context_accumulate_contributions(gsplat_context *c, int num_gaussians
   return gs::launch_contributions(gs::recorded_forward(c), weight_sum, weight_max, pixels, (hipStream_t)stream);
 }
 
+int gsplat_context_median_depth(gsplat_context *c, int num_gaussians, float threshold, float *depth, int *index,
+                                void *stream) {
+  // (every check before the launch: a refused call leaves the caller's arrays as they were)
+  GS_REQUIRE(c != nullptr, "null context");
+  GS_REQUIRE(c->lists_ready, "no forward pass recorded in this context");
+  GS_REQUIRE(num_gaussians == c->N, "does not match the recorded forward");
+  GS_REQUIRE(std::isfinite(threshold) && threshold > 0.0f && threshold < 1.0f, "threshold must lie in (0, 1)");
+  GS_REQUIRE(depth != nullptr && gs::check_device_ptr(depth, "depth", __func__) == GSPLAT_OK,
+             "depth must be a device pointer");
+  GS_REQUIRE(index == nullptr || gs::check_device_ptr(index, "index", __func__) == GSPLAT_OK,
+             "index must be a device pointer or NULL");
+  return gs::launch_median_depth(gs::recorded_forward(c), c->xyz_c.as<float>(), threshold, depth, index,
+                                 (hipStream_t)stream);
+}
+
 int gsplat_context_render_features(gsplat_context *c, int num_gaussians, int channels, const float *features, float *out,
                                    void *stream) {
   // (every check before the launch: a refused call leaves the caller's arrays as they were)

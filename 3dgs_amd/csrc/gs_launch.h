@@ -58,6 +58,9 @@ bool tile_order_supported(int num_tiles);
 
 // ---- gs_replay.hip: the kernels that walk a recorded forward again (gs_render.h: ReplayArgs)
 int launch_contributions(const ReplayArgs &a, float *weight_sum, float *weight_max, int *pixels, hipStream_t st);
+// per pixel the list position of the first composited entry behind which T <= threshold and that gaussian's z from the
+// compacted xyz_c [M,3] (median_depth_kernel): depth [H,W], index [H,W] or null; (0, -1) where T never gets there
+int launch_median_depth(const ReplayArgs &a, const float *xyz_c, float threshold, float *depth, int *index, hipStream_t st);
 // the caller's channels through the recorded forward's weights and back (features_fwd_kernel, features_lift_kernel):
 // features [N,C] in global order -> out [H,W,C]; map [H,W,C] -> lifted [N,C] in global order, accumulated into
 int launch_features_fwd(const ReplayArgs &a, int channels, const float *features, float *out, hipStream_t st);

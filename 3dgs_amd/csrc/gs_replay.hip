@@ -1,5 +1,6 @@
 // gs_replay.hip -- the kernels that walk a recorded forward again (gs_render.h: ReplayArgs), for gfx950:
 //   contributions_kernel   per-gaussian blend-weight statistics          (gsplat_context_accumulate_contributions)
+//   median_depth_kernel    z of the entry at which T falls to a threshold (gsplat_context_median_depth)
 //   features_fwd_kernel    out[p, c]     = sum_i w_ip f[g_i, c]          (gsplat_context_render_features)
 //   features_lift_kernel   lifted[g, c] += sum_p w_gp map[p, c]          (gsplat_context_lift_features)
 //   features_bwd_kernel    the map's gradient with respect to the geometry (gsplat_context_features_backward)
@@ -232,6 +233,62 @@ __global__ __launch_bounds__(256) void contributions_kernel(ReplayArgs a, float 
         if (pixels) atomicAdd(pixels + gi, cnt);
       }
     }
+  }
+}
+
+// ---- median depth: the walk reduced to the first entry behind which the pixel's transmittance has fallen to
+// `threshold`.  z of the batch's gaussians (the compacted xyz_c, as the forward stored it) is staged beside the records in
+// s_z; a lane keeps T, the answer and its list position, and an answer once found is never replaced: no atomics, nothing
+// written but the two maps, the same bits in every run and under either binning route.  A pixel is done when it has its
+// answer or the batch starts at or behind its stop index; a wave whose pixels are all done builds no lists, and the
+// workgroup leaves at the batch's barrier when every pixel is (__syncthreads_and: one decision for the workgroup) -- a
+// done pixel's state cannot change, so the exits change no bit.
+__global__ __launch_bounds__(256) void median_depth_kernel(ReplayArgs a, const float *__restrict__ xyz_c, float threshold,
+                                                           float *__restrict__ depth, int *__restrict__ index) {
+  __shared__ float4 s_r0[kBatch + 1], s_r1[kBatch + 1];  // stage_capped's; [kBatch]: the sentinel
+  __shared__ float s_z[kBatch + 1];
+  __shared__ int s_tile_top;
+  __shared__ __attribute__((aligned(16))) unsigned short s_list[16 * kListStride + 2];
+  const int tile = ordered_tile(nullptr, (int)blockIdx.x, tile_count(a));
+  if (tile >= tile_count(a)) return;
+  const int tid = threadIdx.x;
+  walk_setup<kBatch>(s_r0, s_r1, &s_tile_top);
+  if (tid == 0) s_z[kBatch] = 0.0f;
+  const TilePixel p = tile_pixel(a, tile);
+  WalkTops tops = walk_tops(p.n);
+  __syncthreads();
+  if (p.lane == 0) atomicMax(&s_tile_top, tops.wave);
+  __syncthreads();
+  tops.tile = s_tile_top;
+  const unsigned short *my_list = s_list + (p.wave * 4 + p.row) * kListStride;  // this row's of the wave's four lists
+  float T = p.inside ? 1.0f : 0.0f;
+  float z = 0.0f;
+  int found = -1;
+  for (int base = 0; base < tops.tile; base += kBatch) {
+    const int count = min(kBatch, tops.tile - base);
+    const bool done = found >= 0 || base >= p.n;
+    // (also: the trips of the batch before have read the records and s_z)
+    if (__syncthreads_and(done ? 1 : 0)) break;
+    if (tid < count) {
+      const int g = stage_capped(a, p, base + tid, s_r0, s_r1, tid);
+      s_z[tid] = xyz_c[3 * (size_t)g + 2];
+    }
+    __syncthreads();
+    if (__ballot(!done) == 0ull) continue;
+    const int trips = walk_lists<kListStride>(s_r1, s_list, count, p, tops, base);
+    for (int i = 0; i < trips; ++i) {
+      const int off = my_list[i];
+      bool on;
+      (void)trip_weight(s_r0, s_r1, off, base, p, T, on);
+      if (on && found < 0 && T <= threshold) {
+        found = base + (off >> 4);
+        z = s_z[off >> 4];
+      }
+    }
+  }
+  if (p.inside) {
+    depth[p.pid] = z;
+    if (index) index[p.pid] = found;
   }
 }
 
@@ -541,6 +598,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GS_FEAT_BWD
 int launch_contributions(const ReplayArgs &a, float *weight_sum, float *weight_max, int *pixels, hipStream_t st) {
   contributions_kernel<<<dim3(tile_grid(tile_count(a))), dim3(256), 0, st>>>(a, weight_sum,
                                                                              reinterpret_cast<unsigned int *>(weight_max), pixels);
+  GS_LAUNCH_CHECK();
+  return GSPLAT_OK;
+}
+
+int launch_median_depth(const ReplayArgs &a, const float *xyz_c, float threshold, float *depth, int *index, hipStream_t st) {
+  median_depth_kernel<<<dim3(tile_grid(tile_count(a))), dim3(256), 0, st>>>(a, xyz_c, threshold, depth, index);
   GS_LAUNCH_CHECK();
   return GSPLAT_OK;
 }

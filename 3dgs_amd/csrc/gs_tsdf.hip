@@ -1,5 +1,6 @@
-// gs_tsdf.hip -- TSDF fusion of rendered depth maps (gsplat_tsdf_integrate) and the extraction of the zero level set as an
-// indexed triangle mesh by marching tetrahedra (gsplat_tsdf_mark, gsplat_tsdf_emit); definitions: include/gsplat_hip.h.
+// gs_tsdf.hip -- TSDF fusion of rendered depth maps (gsplat_tsdf_integrate; gsplat_tsdf_integrate_surface for maps that
+// hold the surface depth itself) and the extraction of the zero level set as an indexed triangle mesh by marching
+// tetrahedra (gsplat_tsdf_mark, gsplat_tsdf_emit); definitions: include/gsplat_hip.h.
 //
 // Like gs_normal.hip, every decision and every value is evaluated in double from the float inputs and rounded to float
 // once.  Every kernel GATHERS: a thread owns a grid node (x on the lanes: a wave's loads and stores of the volume are one
@@ -29,6 +30,8 @@ constexpr int kTX = 64, kTY = 4;    // a block: 64 nodes along x (one wave per r
 struct TsdfView { float m[12]; float fx, fy, cx, cy; };  // row-major [R|t], pixel intrinsics
 struct TsdfBatch { TsdfView v[kTsdfViews]; int n; };
 struct TsdfVolume { double ox, oy, oz, voxel; int nx, ny, nz; };
+// inverse: kTsdfExpected (depth = sum alpha T z), kTsdfInverse (sum alpha T / z), kTsdfSurface (the surface depth itself)
+enum { kTsdfExpected = 0, kTsdfInverse = 1, kTsdfSurface = 2 };
 struct TsdfRule { double alpha_min, trunc, near, max_depth; float max_weight; int inverse; };
 
 // block -> the node of this thread; false outside the grid
@@ -69,9 +72,17 @@ __global__ __launch_bounds__(kTX * kTY) void tsdf_integrate_kernel(TsdfVolume vo
     const double fv = floor(((double)cam.fy * yc / z + (double)cam.cy) + 0.5);
     if (!(fu >= 0.0 && fu < (double)W && fv >= 0.0 && fv < (double)H)) continue;
     const size_t pix = (size_t)v * P + (size_t)((int)fv) * W + (size_t)((int)fu);
-    const double A = 1.0 - (double)T[pix], d = (double)depth[pix];
-    if (!(A >= rule.alpha_min && A < HUGE_VAL && d > 0.0 && d < HUGE_VAL)) continue;
-    const double surf = rule.inverse ? A / d : d / A;
+    const double d = (double)depth[pix];
+    double surf;
+    if (rule.inverse == kTsdfSurface) {  // (T may be null: no opacity gate)
+      if (!(d > 0.0 && d < HUGE_VAL)) continue;
+      if (T != nullptr && !(1.0 - (double)T[pix] >= rule.alpha_min)) continue;
+      surf = d;
+    } else {
+      const double A = 1.0 - (double)T[pix];
+      if (!(A >= rule.alpha_min && A < HUGE_VAL && d > 0.0 && d < HUGE_VAL)) continue;
+      surf = rule.inverse ? A / d : d / A;
+    }
     if (rule.max_depth > 0.0 && surf > rule.max_depth) continue;
     const double s = surf - z;
     if (!(s >= -rule.trunc)) continue;
@@ -329,31 +340,30 @@ unsigned int grid_blocks(int nx, int ny, int nz) {
   return (unsigned int)((long long)gs::div_up(nx, kTX) * gs::div_up(ny, kTY) * nz);  // <= the node count
 }
 
-}  // namespace
-
-extern "C" {
-
-int gsplat_tsdf_integrate(float *tsdf, float *weight, float *color, int nx, int ny, int nz, const float *origin, float voxel,
-                          const float *depth, const float *T, const float *image, const float *view,
-                          const float *intrinsics, int num_views, int rows, int cols, int inverse, float alpha_min,
-                          float trunc, float near, float max_depth, float max_weight, void *stream) {
-  if (int rc = check_grid(__func__, nx, ny, nz, voxel)) return rc;
-  GS_REQUIRE(rows > 0 && cols > 0 && num_views >= 0, "image size must be positive, num_views not negative");
-  GS_REQUIRE(std::isfinite(trunc) && trunc > 0.0f, "trunc must be finite and positive");
-  GS_REQUIRE(alpha_min > 0.0f && alpha_min <= 1.0f, "alpha_min must lie in (0, 1]");
-  GS_REQUIRE((image != nullptr) == (color != nullptr), "image and color go together");
+// gsplat_tsdf_integrate (mode kTsdfExpected / kTsdfInverse) and gsplat_tsdf_integrate_surface (kTsdfSurface, T may be null)
+int integrate(const char *fn, float *tsdf, float *weight, float *color, int nx, int ny, int nz, const float *origin,
+              float voxel, const float *depth, const float *T, const float *image, const float *view,
+              const float *intrinsics, int num_views, int rows, int cols, int mode, float alpha_min, float trunc, float near,
+              float max_depth, float max_weight, void *stream) {
+  if (int rc = check_grid(fn, nx, ny, nz, voxel)) return rc;
+  GS_REQUIRE_IN(fn, rows > 0 && cols > 0 && num_views >= 0, "image size must be positive, num_views not negative");
+  GS_REQUIRE_IN(fn, std::isfinite(trunc) && trunc > 0.0f, "trunc must be finite and positive");
+  GS_REQUIRE_IN(fn, alpha_min > 0.0f && alpha_min <= 1.0f, "alpha_min must lie in (0, 1]");
+  GS_REQUIRE_IN(fn, (image != nullptr) == (color != nullptr), "image and color go together");
   if (num_views == 0) return GSPLAT_OK;
-  GS_REQUIRE(tsdf && weight && origin && depth && T && view && intrinsics, "a required pointer is NULL");
+  GS_REQUIRE_IN(fn, tsdf && weight && origin && depth && (T || mode == kTsdfSurface) && view && intrinsics,
+                "a required pointer is NULL");
   for (int v = 0; v < num_views; ++v) {
     const float *k = intrinsics + 4 * v;
-    GS_REQUIRE(std::isfinite(k[0]) && std::isfinite(k[1]) && std::isfinite(k[2]) && std::isfinite(k[3]),
+    GS_REQUIRE_IN(fn, std::isfinite(k[0]) && std::isfinite(k[1]) && std::isfinite(k[2]) && std::isfinite(k[3]),
                "the intrinsics must be finite");
-    GS_REQUIRE(k[0] != 0.0f && k[1] != 0.0f, "fx and fy must not be 0");
+    GS_REQUIRE_IN(fn, k[0] != 0.0f && k[1] != 0.0f, "fx and fy must not be 0");
   }
-  GS_REQUIRE_DEV(tsdf); GS_REQUIRE_DEV(weight); GS_REQUIRE_DEV(depth); GS_REQUIRE_DEV(T);
-  if (color) { GS_REQUIRE_DEV(color); GS_REQUIRE_DEV(image); }
+  GS_REQUIRE_DEV_IN(fn, tsdf); GS_REQUIRE_DEV_IN(fn, weight); GS_REQUIRE_DEV_IN(fn, depth);
+  if (T) GS_REQUIRE_DEV_IN(fn, T);
+  if (color) { GS_REQUIRE_DEV_IN(fn, color); GS_REQUIRE_DEV_IN(fn, image); }
   const TsdfVolume vol = {(double)origin[0], (double)origin[1], (double)origin[2], (double)voxel, nx, ny, nz};
-  const TsdfRule rule = {(double)alpha_min, (double)trunc, (double)near, (double)max_depth, max_weight, inverse != 0};
+  const TsdfRule rule = {(double)alpha_min, (double)trunc, (double)near, (double)max_depth, max_weight, mode};
   const dim3 block(kTX, kTY);
   const unsigned int blocks = grid_blocks(nx, ny, nz);
   const size_t P = (size_t)rows * cols;
@@ -367,7 +377,7 @@ int gsplat_tsdf_integrate(float *tsdf, float *weight, float *color, int nx, int 
       const float *k = intrinsics + 4 * (size_t)src;
       batch.v[v].fx = k[0]; batch.v[v].fy = k[1]; batch.v[v].cx = k[2]; batch.v[v].cy = k[3];
     }
-    const float *d = depth + base * P, *t = T + base * P;
+    const float *d = depth + base * P, *t = T ? T + base * P : nullptr;
     if (color)
       tsdf_integrate_kernel<true><<<blocks, block, 0, st>>>(vol, rule, batch, d, t, image + base * P * 3, rows, cols, tsdf,
                                                             weight, color);
@@ -377,6 +387,27 @@ int gsplat_tsdf_integrate(float *tsdf, float *weight, float *color, int nx, int 
     GS_LAUNCH_CHECK();
   }
   return GSPLAT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gsplat_tsdf_integrate(float *tsdf, float *weight, float *color, int nx, int ny, int nz, const float *origin, float voxel,
+                          const float *depth, const float *T, const float *image, const float *view,
+                          const float *intrinsics, int num_views, int rows, int cols, int inverse, float alpha_min,
+                          float trunc, float near, float max_depth, float max_weight, void *stream) {
+  return integrate(__func__, tsdf, weight, color, nx, ny, nz, origin, voxel, depth, T, image, view, intrinsics, num_views,
+                   rows, cols, inverse != 0 ? kTsdfInverse : kTsdfExpected, alpha_min, trunc, near, max_depth, max_weight,
+                   stream);
+}
+
+int gsplat_tsdf_integrate_surface(float *tsdf, float *weight, float *color, int nx, int ny, int nz, const float *origin,
+                                  float voxel, const float *depth, const float *T, const float *image, const float *view,
+                                  const float *intrinsics, int num_views, int rows, int cols, float alpha_min, float trunc,
+                                  float near, float max_depth, float max_weight, void *stream) {
+  return integrate(__func__, tsdf, weight, color, nx, ny, nz, origin, voxel, depth, T, image, view, intrinsics, num_views,
+                   rows, cols, kTsdfSurface, alpha_min, trunc, near, max_depth, max_weight, stream);
 }
 
 int gsplat_tsdf_views_per_pass(void) { return kTsdfViews; }

@@ -582,7 +582,7 @@ def _host_rows(t, name, rows, cols):
 
 
 def tsdf_integrate(volume, depth, T, view, intrinsics, image=None, inverse=False, alpha_min=0.5, trunc=None, near=0.0,
-                   max_depth=0.0, max_weight=0.0):
+                   max_depth=0.0, max_weight=0.0, surface=False):
     """Fuse K views of one size into `volume` in place (gsplat_tsdf_integrate): depth, T [K,H,W] as a depth-mode forward
     renders them (`inverse`: the forward composited 1/z), image [K,H,W,3] exactly when the volume has colour, view [K,12]
     row-major [R|t] (the first twelve numbers of a camera dict's view), intrinsics [K,4] as pixel_intrinsics gives them.
@@ -590,9 +590,18 @@ def tsdf_integrate(volume, depth, T, view, intrinsics, image=None, inverse=False
     depth > 0) and its surface depth d = depth / (1 - T) is at most max_depth (<= 0: no limit) and d - z >= -trunc; then
     tsdf = (w tsdf + min(1, (d - z) / trunc)) / (w + 1), colour likewise, w = min(w + 1, max_weight) (<= 0: no cap).
     trunc: 4 voxels unless given.  The volume is read and written once per gsplat_tsdf_views_per_pass() views, and a batch
-    is bit for bit its views one call at a time.  Returns the volume."""
+    is bit for bit its views one call at a time.  Returns the volume.
+    surface=True (gsplat_tsdf_integrate_surface): depth holds the surface depth d itself -- RasterContext.median_depth's
+    map, or sensor depth -- and a pixel is ok when depth is finite and > 0 and either T is None (no opacity gate) or
+    1 - T >= alpha_min; `inverse` must then be left False."""
+    if surface and inverse:
+        raise ValueError("surface=True takes the surface depth itself: inverse must be False")
+    if T is None and not surface:
+        raise ValueError("T may be None only with surface=True")
     tsdf, weight, color, (nx, ny, nz), origin = _tsdf_grid(volume)
     for t, name in ((depth, "depth"), (T, "T")):
+        if t is None and name == "T":
+            continue
         if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()
                 or t.dim() != 3 or t.shape != depth.shape):
             raise ValueError(f"{name} must be a contiguous [K,H,W] float32 device tensor")
@@ -607,6 +616,12 @@ def tsdf_integrate(volume, depth, T, view, intrinsics, image=None, inverse=False
     view_a, view_p = _host_rows(view, "view", K, 12)
     intr_a, intr_p = _host_rows(intrinsics, "intrinsics", K, 4)
     trunc = 4.0 * volume["voxel"] if trunc is None else trunc
+    if surface:
+        check(_lib.load().gsplat_tsdf_integrate_surface(
+            _p(tsdf), _p(weight), _p(color), nx, ny, nz, origin, float(volume["voxel"]), _p(depth), _p(T), _p(image),
+            view_p, intr_p, K, H, W, float(alpha_min), float(trunc), float(near), float(max_depth), float(max_weight),
+            _stream()))
+        return volume
     check(_lib.load().gsplat_tsdf_integrate(
         _p(tsdf), _p(weight), _p(color), nx, ny, nz, origin, float(volume["voxel"]), _p(depth), _p(T), _p(image), view_p,
         intr_p, K, H, W, int(bool(inverse)), float(alpha_min), float(trunc), float(near), float(max_depth),
@@ -645,6 +660,87 @@ def tsdf_extract(volume, min_weight=1.0):
                                    float(volume["voxel"]), _p(cell_ok), _p(edge_mask), _p(vert_offset), _p(tri_offset),
                                    num_vertices, num_faces, _p(vertices), _p(colors), _p(faces), _stream()))
     return vertices, faces, colors
+
+
+def _mesh_faces(faces, num_vertices):
+    if (not isinstance(faces, torch.Tensor) or faces.dtype != torch.int32 or not faces.is_cuda or not faces.is_contiguous()
+            or faces.dim() != 2 or faces.shape[1] != 3):
+        raise ValueError("faces must be a contiguous [Nf,3] int32 device tensor")
+    if isinstance(num_vertices, bool) or not isinstance(num_vertices, int) or num_vertices < 0:
+        raise ValueError("num_vertices must be a non-negative integer")
+    if faces.shape[0] and not num_vertices:
+        raise ValueError("faces without vertices")
+
+
+def mesh_components(faces, num_vertices):
+    """The connected components of an indexed mesh (gsplat_mesh_components): faces [Nf,3] int32 on the device into
+    num_vertices vertices -> dict(label [Nv] int32: the smallest vertex index of the vertex's component, two vertices being
+    connected when a face holds both and a vertex in no face labelling itself; face_count [Nv] int32: at a label the number
+    of faces of its component, 0 elsewhere; rounds: the hook rounds that ran).  A lock-free union-find, a flatten and a
+    count launch; integers only: the same bits in every run.  A face index outside [0, num_vertices) is an error (-3)
+    found on the device before anything is written; that check is the call's one read-back."""
+    _mesh_faces(faces, num_vertices)
+    label = torch.empty(num_vertices, dtype=torch.int32, device=faces.device)
+    face_count = torch.empty(num_vertices, dtype=torch.int32, device=faces.device)
+    rounds = ctypes.c_int(0)
+    check(_lib.load().gsplat_mesh_components(_p(faces), int(faces.shape[0]), num_vertices, _p(label), _p(face_count),
+                                             ctypes.byref(rounds), _stream()))
+    return dict(label=label, face_count=face_count, rounds=int(rounds.value))
+
+
+def mesh_filter(vertices, faces, colors=None, min_faces=0, keep_largest=0):
+    """Drop connected components of an indexed mesh -> (vertices, faces, colors, report).  A component (mesh_components)
+    is kept iff its face_count >= min_faces and, when keep_largest > 0, it is among the keep_largest components ranked by
+    (-face_count, label); an unreferenced vertex is a component of 0 faces.  Kept vertices, colours and faces keep their
+    order, the face indices are renumbered (gsplat_mesh_compact).  The selection is torch on the device (one sort over the
+    vertices, no host loop over components), the prefix sums are torch.cumsum, and one read-back fetches the new sizes.
+    report: dict(components, kept, faces_removed, vertices_removed).  With min_faces and keep_largest both 0 the inputs
+    are returned as they are and nothing is launched (report: None)."""
+    for name, v in (("min_faces", min_faces), ("keep_largest", keep_largest)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError(f"{name} must be a non-negative integer")
+    if (not isinstance(vertices, torch.Tensor) or vertices.dtype != torch.float32 or not vertices.is_cuda
+            or not vertices.is_contiguous() or vertices.dim() != 2 or vertices.shape[1] != 3):
+        raise ValueError("vertices must be a contiguous [Nv,3] float32 device tensor")
+    nv = int(vertices.shape[0])
+    _mesh_faces(faces, nv)
+    if colors is not None and (not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32 or not colors.is_cuda
+                               or not colors.is_contiguous() or tuple(colors.shape) != (nv, 3)):
+        raise ValueError("colors must be a contiguous [Nv,3] float32 device tensor or None")
+    if min_faces == 0 and keep_largest == 0:
+        return vertices, faces, colors, None
+    dev, nf = vertices.device, int(faces.shape[0])
+    comp = mesh_components(faces, nv)
+    label, count = comp["label"].long(), comp["face_count"].long()
+    ids = torch.arange(nv, dtype=torch.int64, device=dev)
+    is_root = label == ids
+    keep_root = is_root & (count >= min_faces)
+    if keep_largest > 0:  # rank the roots by (-face_count, label); every non-root sorts behind them
+        key = torch.where(is_root, (nf - count) * max(nv, 1) + ids, torch.full_like(ids, torch.iinfo(torch.int64).max))
+        rank = torch.empty_like(ids)
+        rank[torch.argsort(key)] = ids
+        keep_root &= rank < keep_largest
+    keep_vertex = keep_root[label]
+    keep_face = keep_vertex[faces[:, 0].long()] if nf else torch.zeros(0, dtype=torch.bool, device=dev)
+    vertex_offset = torch.cumsum(keep_vertex, 0, dtype=torch.int64)
+    face_offset = torch.cumsum(keep_face, 0, dtype=torch.int64)
+    zero = torch.zeros((), dtype=torch.int64, device=dev)
+    new_nv, new_nf, components, kept = (int(v) for v in torch.stack((
+        vertex_offset[-1] if nv else zero, face_offset[-1] if nf else zero, is_root.sum(), keep_root.sum())).tolist())
+    keep_u8 = keep_vertex.to(torch.uint8)
+    vertex_offset -= keep_u8  # inclusive -> exclusive
+    face_offset -= keep_face.to(torch.uint8)
+    out_v = torch.empty(new_nv, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(new_nf, 3, dtype=torch.int32, device=dev)
+    out_c = None if colors is None else torch.empty(new_nv, 3, dtype=torch.float32, device=dev)
+    if new_nv:
+        some_faces = new_nf > 0
+        check(_lib.load().gsplat_mesh_compact(
+            _p(vertices), _p(colors), _p(faces) if some_faces else None, nv, nf if some_faces else 0,
+            _p(keep_u8), _p(vertex_offset), _p(face_offset) if some_faces else None, _p(out_v),
+            _p(out_c), _p(out_f) if some_faces else None, _stream()))
+    report = dict(components=components, kept=kept, faces_removed=nf - new_nf, vertices_removed=nv - new_nv)
+    return out_v, out_f, out_c, report
 
 
 def compute_psnr(predicted_data, gt_data, rows, cols):

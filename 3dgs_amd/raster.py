@@ -237,6 +237,30 @@ class RasterContext:
         check(self._lib.gsplat_context_accumulate_contributions(self._h, int(n), _ptr(weight_sum), _ptr(weight_max),
                                                                 _ptr(pixels), st))
 
+    def median_depth(self, threshold=0.5, out=None, index=None):
+        """The median (quantile) depth map of the last forward (gsplat_context_median_depth) -> [H,W] float32: per pixel
+        the camera-space z of the first composited gaussian behind which the transmittance is <= threshold (0.5: the
+        median), 0 where it never gets there.  Always z, whatever the context's depth mode; depth mode is not needed.
+        `out`: an [H,W] float32 device tensor to write into, else a new one; returned.  `index`: an [H,W] int32 device
+        tensor that receives that gaussian's position in its tile's list, -1 where there is none.  No atomics: the
+        same bits in every run.  Works after any forward (render-only included), before or after its backward."""
+        import math
+        threshold = float(threshold)
+        if not (math.isfinite(threshold) and 0.0 < threshold < 1.0):
+            raise ValueError("threshold must be finite and in (0, 1), not %r" % threshold)
+        H, W = self._feature_map_shape()
+        for name, t, dt in (("out", out, torch.float32), ("index", index, torch.int32)):
+            if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_cuda
+                                  or not t.is_contiguous() or tuple(t.shape) != (H, W)):
+                raise ValueError("%s must be a contiguous [%d,%d] %s device tensor or None"
+                                 % (name, H, W, str(dt).split(".")[1]))
+        if out is None:
+            out = torch.empty(H, W, dtype=torch.float32, device="cuda")
+        n = self._last[0] if self._last else 0
+        st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self._lib.gsplat_context_median_depth(self._h, int(n), threshold, _ptr(out), _ptr(index), st))
+        return out
+
     @staticmethod
     def _dense(name, t, dims):
         if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous()

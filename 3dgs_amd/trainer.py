@@ -791,8 +791,21 @@ class Trainer:
                 ctx.set_depth(False)
             ctx.set_render_only(False)
 
+    def render_median_depth(self, cam, threshold=0.5):
+        """The [H,W] median depth map of the current gaussians from `cam` (RasterContext.median_depth on a render-only
+        forward at background 0, in the mode the run trains in): camera-space z of the gaussian at which the
+        transmittance falls to `threshold`, 0 where it never does.  The context's flags are as before afterwards."""
+        ctx = self._context_for(self.num_gaussians)
+        ctx.set_render_only(True)
+        try:
+            ctx.rasterize_image(dict(self.params), cam, self.cfg, 0.0, self.l_max)
+            return ctx.median_depth(threshold)
+        finally:
+            ctx.set_render_only(False)
+
     def extract_mesh(self, path=None, resolution=256, bounds=None, voxel=None, trunc=None, views=None, alpha_min=None,
-                     max_depth=None, min_weight=1.0, batch=4, color=True):
+                     max_depth=None, min_weight=1.0, batch=4, color=True, depth="expected", median_threshold=0.5,
+                     min_component_faces=0, keep_largest=0):
         """A triangle mesh of the current gaussians: the depth maps of `views` ((camera, ...) tuples or camera dicts;
         default: the training views) fused into a TSDF volume (ops.tsdf_integrate) whose zero level set is extracted by
         marching tetrahedra (ops.tsdf_extract) -- the last step of 2DGS, RaDe-GS and GOF, what the depth, distortion and
@@ -810,11 +823,25 @@ class Trainer:
         an explicit box around what is to be meshed.  voxel: the longest side / resolution unless given.  trunc:
         4 voxels unless given -- a choice inside the 4..5 voxels the examples of Open3D and 2DGS use, not a tuned value.
         alpha_min: config key normal_alpha_min unless given.  max_depth: surface depths beyond it are ignored (None: no
-        limit).  min_weight: a cell is meshed when all its eight nodes were observed that often.  One rank only."""
+        limit).  min_weight: a cell is meshed when all its eight nodes were observed that often.  One rank only.
+        depth: "expected" fuses the expected depth sum alpha T z / (1 - T) as above; "median" fuses the median depth
+        (RasterContext.median_depth at median_threshold: z of the gaussian at which the transmittance falls through it)
+        with the surface form of the integration, gated by 1 - T >= alpha_min -- the context is not put into depth mode
+        for it.  min_component_faces, keep_largest: ops.mesh_filter on the extracted mesh before it is written (both 0:
+        no filter); its report is returned under the key `filter` (None without a filter)."""
         import math
         from . import mesh as mesh_io
         if self.world > 1:
             raise ValueError("extract_mesh runs on one rank only")
+        if depth not in ("expected", "median"):
+            raise ValueError('depth must be "expected" or "median"')
+        median = depth == "median"
+        median_threshold = float(median_threshold)
+        if median and not (math.isfinite(median_threshold) and 0.0 < median_threshold < 1.0):
+            raise ValueError("median_threshold must be finite and in (0, 1)")
+        for name, v in (("min_component_faces", min_component_faces), ("keep_largest", keep_largest)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"{name} must be a non-negative integer")
         if not isinstance(batch, int) or batch < 1:
             raise ValueError("batch must be a positive integer")
         cams = [v if isinstance(v, dict) else v[0] for v in (self.views if views is None else views)]
@@ -851,13 +878,13 @@ class Trainer:
                     d, t, im = bufs[size]
                     ops.tsdf_integrate(volume, d[:k], t[:k], np.stack([p[0] for p in pending]),
                                        np.asarray([p[1] for p in pending], np.float32), image=im[:k] if color else None,
-                                       inverse=inverse, alpha_min=alpha_min, trunc=trunc, near=0.0,
-                                       max_depth=0.0 if max_depth is None else float(max_depth))
+                                       inverse=inverse and not median, alpha_min=alpha_min, trunc=trunc, near=0.0,
+                                       max_depth=0.0 if max_depth is None else float(max_depth), surface=median)
                     del pending[:]
 
             ctx.set_render_only(True)
             try:
-                if not mode[0]:  # a run without depth terms: depth mode for these forwards only
+                if not mode[0] and not median:  # a run without depth terms: depth mode for these forwards only
                     ctx.set_depth(True, inverse=inverse)
                 size = None
                 for cam in cams:
@@ -875,20 +902,25 @@ class Trainer:
                         z = lambda *s: torch.empty(batch, *s, dtype=torch.float32, device=dev)
                         bufs[size] = (z(*size), z(*size), z(*size, 3) if color else None)
                     k = len(pending)
-                    bufs[size][0][k].copy_(fwd["depth"])
+                    if median:
+                        ctx.median_depth(median_threshold, out=bufs[size][0][k])
+                    else:
+                        bufs[size][0][k].copy_(fwd["depth"])
                     bufs[size][1][k].copy_(fwd["T"])
                     if color:
                         bufs[size][2][k].copy_(fwd["image"])
                     pending.append((host(cam["view"]).reshape(-1)[:12].astype(np.float32), self._intrinsics_of(cam)))
                 flush(size)
             finally:
-                if not mode[0]:
+                if not mode[0] and not median:
                     ctx.set_depth(False)
                 ctx.set_render_only(False)
         vertices, faces, colors = ops.tsdf_extract(volume, min_weight=min_weight)
+        vertices, faces, colors, report = ops.mesh_filter(vertices, faces, colors, min_faces=min_component_faces,
+                                                          keep_largest=keep_largest)
         if path is not None:
             mesh_io.save_ply(path, vertices, faces, colors)
-        return dict(vertices=vertices, faces=faces, colors=colors, volume=volume)
+        return dict(vertices=vertices, faces=faces, colors=colors, volume=volume, filter=report)
 
     def contribution_scores(self, views=None):
         """dict(weight_sum, weight_max, pixels): [N] device tensors, the blend-weight statistics of every gaussian

@@ -659,6 +659,26 @@ int gsplat_backward_pass_camera(gsplat_context *ctx, const gsplat_gaussians *gau
 int gsplat_context_accumulate_contributions(gsplat_context *ctx, int num_gaussians, float *weight_sum,
                                             float *weight_max, int *pixels, void *stream);
 
+/* Median (quantile) depth of the last completed forward (no ABI bump: a new entry point only): the depth 2DGS, RaDe-GS
+ * and gsplat mesh from, where the expected depth sum alpha T z / (1 - T) lies in front of the surface.  For pixel p walk
+ * the composited entries of its tile's list front to back as gsplat_context_accumulate_contributions does (entry i is
+ * composited iff i < splats_per_pixel[p] and its alpha passes the forward's 1/255 test; alpha capped at 0.99,
+ * T <- fma(-alpha, T, T) from T = 1):
+ *   index[p]  the list position of the first composited entry whose T AFTER it is <= threshold (float32, on that chain);
+ *   depth[p]  the camera-space z of that entry's gaussian, bit for bit as the forward stored it -- always z, never 1/z,
+ *             whatever the context's depth mode, and the context need not be in depth mode at all.
+ * A pixel whose transmittance never reaches the threshold gets depth 0 and index -1 (every visible gaussian has
+ * z > near_thresh > 0: 0 is "no surface here").  threshold must be finite and in (0, 1); 0.5 is the median.  depth and
+ * index are [H,W] device arrays of the recorded forward's size, every pixel is written; index may be NULL.  No atomics:
+ * the same bits in every run and under either binning route.  For a list the forward walked whole T is the forward's bit
+ * for bit, so index[p] >= 0 exactly where weight_per_pixel[p] <= threshold; a segmented forward multiplied its segments'
+ * products in another order.  Calling conditions and `stream` as for gsplat_context_accumulate_contributions; refused
+ * with GSPLAT_ERR_INVALID_ARG before any launch (the arrays stay as they were): a null context, no recorded forward,
+ * another num_gaussians, a threshold outside (0, 1) or not finite, a null or non-device depth, a non-device index.  A
+ * tile list longer than 1488 entries is walked whole by one workgroup. */
+int gsplat_context_median_depth(gsplat_context *ctx, int num_gaussians, float threshold, float *depth /* [H,W] */,
+                                int *index /* [H,W] or NULL */, void *stream);
+
 /* Feature maps of the last completed forward (no ABI bump: new entry points only): the caller's own per-gaussian
  * channels carried through the renderer, and pixel maps lifted back onto the gaussians.  With w_jp the blend weight of
  * gsplat_context_accumulate_contributions above (same entries, same alpha, same T):
@@ -870,6 +890,16 @@ int gsplat_tsdf_integrate(float *tsdf, float *weight, float *color /* or NULL */
                           const float *image /* or NULL */, const float *view, const float *intrinsics, int num_views,
                           int rows, int cols, int inverse, float alpha_min, float trunc, float near, float max_depth,
                           float max_weight, void *stream);
+/* gsplat_tsdf_integrate for a depth map that already holds the surface (a median depth map of
+ * gsplat_context_median_depth, or sensor depth): depth[v,y,x] is the camera-space surface depth d itself.  A pixel is ok
+ * when depth is finite and > 0 and either T is NULL (no opacity gate) or 1 - T >= alpha_min.  Everything else -- trunc,
+ * carving, max_depth, max_weight, colour, evaluation in double, up to gsplat_tsdf_views_per_pass() views per pass, a batch
+ * bit for bit its views one call at a time, the refusals (T excepted) -- is gsplat_tsdf_integrate's: one kernel. */
+int gsplat_tsdf_integrate_surface(float *tsdf, float *weight, float *color /* or NULL */, int nx, int ny, int nz,
+                                  const float *origin, float voxel, const float *depth, const float *T /* or NULL */,
+                                  const float *image /* or NULL */, const float *view, const float *intrinsics,
+                                  int num_views, int rows, int cols, float alpha_min, float trunc, float near,
+                                  float max_depth, float max_weight, void *stream);
 int gsplat_tsdf_views_per_pass(void);
 int gsplat_tsdf_mark(const float *tsdf, const float *weight, int nx, int ny, int nz, float min_weight,
                      unsigned char *cell_ok, int *tri_count, unsigned char *edge_mask, int *vert_count, void *stream);
@@ -877,6 +907,33 @@ int gsplat_tsdf_emit(const float *tsdf, const float *color /* or NULL */, int nx
                      float voxel, const unsigned char *cell_ok, const unsigned char *edge_mask,
                      const long long *vert_offset, const long long *tri_offset, long long num_vertices,
                      long long num_faces, float *vertices, float *vertex_colors /* or NULL */, int *faces, void *stream);
+
+/* Connected components of an indexed triangle mesh and the gather that drops components (no ABI bump: new entry points
+ * only; gs_mesh.hip) -- the cleanup every meshing pipeline ends with (2DGS's post_process_mesh keeps the largest clusters).
+ *   gsplat_mesh_components  faces [num_faces,3] int32 into num_vertices vertices, device arrays.  Two vertices are
+ *                     connected when a face contains both (connectivity by shared vertices; on a marching-tetrahedra
+ *                     mesh it differs from edge adjacency only at non-manifold pinch points).  label[v] = the smallest
+ *                     vertex index of v's component (a vertex in no face labels itself); face_count[r] = the number of
+ *                     faces of the component whose label is r, 0 at every index that is not a label.  Integers, with
+ *                     integer atomics: the same bits in every run whatever the order.  A lock-free union-find (the larger
+ *                     root hooked under the smaller by compare-and-swap, paths halved on the way) then a flatten and a
+ *                     count launch: the work does not grow with the mesh's diameter; *rounds (host, may be NULL) = the
+ *                     number of hook rounds, 1.  A face index outside [0, num_vertices) makes the call fail with
+ *                     GSPLAT_ERR_INVALID_ARG: a checking launch and the call's one read-back come first, label and
+ *                     face_count are then untouched.  Also refused: negative sizes, a NULL or non-device label or
+ *                     face_count (num_vertices > 0) or faces (num_faces > 0).  Synchronises `stream`.
+ *   gsplat_mesh_compact  the gather: keep_vertex [num_vertices] (0 / 1), vertex_offset its exclusive prefix sum; a face is
+ *                     kept iff its first vertex is (the three vertices of a face share a label, so a selection by
+ *                     component is constant over a face), face_offset [num_faces] the exclusive prefix sum of that.  Kept
+ *                     vertices, colours (colors and out_colors NULL together) and faces keep their relative order, face
+ *                     indices go through vertex_offset.  The outputs hold the kept counts (the caller scans and reads the
+ *                     totals back).  No atomics: the same bits in every run. */
+int gsplat_mesh_components(const int *faces, int num_faces, int num_vertices, int *label /* [Nv] */,
+                           int *face_count /* [Nv] */, int *rounds /* host, may be NULL */, void *stream);
+int gsplat_mesh_compact(const float *vertices, const float *colors /* or NULL */, const int *faces, int num_vertices,
+                        int num_faces, const unsigned char *keep_vertex /* [Nv] */,
+                        const long long *vertex_offset /* [Nv] */, const long long *face_offset /* [Nf] */,
+                        float *out_vertices, float *out_colors /* or NULL */, int *out_faces, void *stream);
 
 /* Binning route of the fused forward.  0 (default): automatic -- the LDS counting sort + per-tile depth sort, or, when
  * the previous forward had more than ~768 list entries per tile (dense real scenes) or the tile grid exceeds 16384
